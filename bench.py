@@ -22,6 +22,11 @@ JSON grammar (sampled tokens bounded by the schema's slot sizes).
 A "step" = every one of the 64 workers completes one task (64 tasks). W warmup
 steps are untimed; K steps are timed between barrier + device synchronize on all
 ranks; the reported time is the max over ranks. Rank 0 prints one JSON line.
+
+A plain run does only that: set up, warm up, time the K steps, print the line. `--seed`
+fixes the documents (the same arguments give the same inputs in every run), `--dump-outputs
+DIR` writes the clients' tasks of the last timed step before the line is printed (see
+dump_outputs), and `--full` is where anything measured beside the headline figure belongs.
 """
 from __future__ import annotations
 
@@ -49,7 +54,7 @@ def synth_document(rng: random.Random, n_words: int) -> str:
     return " ".join(rng.choice(_WORDS) for _ in range(n_words))
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
@@ -84,6 +89,13 @@ def parse():
                     help="pipelined engine steps (schedule/launch step N+1 while step N runs); default: engine's")
     ap.add_argument("--align-slack", type=int, default=96)
     ap.add_argument("--cpu", action="store_true", help="tiny model on CPU (plumbing smoke only)")
+    ap.add_argument("--seed", type=int, default=20517,
+                    help="workload seed: with the same arguments every run submits the same documents")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write each client's task of the last timed step: its reproducible "
+                         "part as DIR/<name>.npy, the sampled replies as DIR/task_replies.jsonl (see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also take the measurements beside the headline figure (none today: same as a plain run)")
     ap.add_argument("--dp-mode", choices=["node", "independent"], default="node",
                     help="node: one manager over the node-wide pool; independent: one Serve per rank")
     ap.add_argument("--reply-tokens", type=int, default=None,
@@ -120,7 +132,7 @@ def parse():
                          "the manager Serve, the control plane and all clients; ranks > 0 are CPU processes whose "
                          "agents answer with model-free schema LLMs after this many seconds per call (the measured "
                          "per-call latency of an 8-worker GPU rank). Use with PILOTTAI_DIST_BACKEND=gloo.")
-    return ap.parse_args()
+    return ap.parse_args(argv)
 
 
 async def run_rank(a, rank: int, world: int, device, tp=None, dp_group=None):
@@ -252,11 +264,12 @@ async def run_rank(a, rank: int, world: int, device, tp=None, dp_group=None):
         serve = Serve(agents=agents, manager_llm=llm, config={**serve_cfg, "max_concurrent_tasks": n_local})
         await serve.start()
     # shared-context broadcast: rank 0 fixes the workload seed for every rank
-    seed = await coll(comm.broadcast_object, int(time.time()) & 0xFFFF if rank == 0 else None)
+    seed = await coll(comm.broadcast_object, a.seed & 0xFFFF if rank == 0 else None)
     init_s = time.time() - t_init
     n_clients = a.workers if node else n_local  # node mode: all 64 clients talk to the one manager
 
     latencies = []
+    last_results = {}  # client -> (document, TaskResult) of its latest timed task (--dump-outputs)
 
     async def client(ci: int, n_tasks: int, rec: bool):
         rng = random.Random(seed * 1000003 + rank * 1009 + ci * 7 + (0 if rec else 99991))
@@ -269,6 +282,7 @@ async def run_rank(a, rank: int, world: int, device, tp=None, dp_group=None):
                 raise RuntimeError(f"task failed: {r.error}")
             if rec:
                 latencies.append(dt)
+                last_results[ci] = (doc, r)
 
     async def round_(n, rec):
         if serve is not None and not (node and drank > 0):
@@ -391,6 +405,8 @@ async def run_rank(a, rank: int, world: int, device, tp=None, dp_group=None):
     local = {
         "dt": dt, "tasks": len(latencies), "lat": latencies, "init_s": init_s, "requeued": requeued,
         "device": _device_identity(device),
+        "last_results": [_result_record(rank, ci, *last_results[ci]) for ci in sorted(last_results)]
+        if a.dump_outputs else [],
         "mem_rows": memory.index.count if memory is not None else 0,
         "loop_lag": sorted(lags), "executions_by_rank": by_rank,
         "managers": 1 if serve is not None else 0, "dp_mode": a.dp_mode if dworld > 1 else "single",
@@ -462,6 +478,75 @@ async def run_cpu_rank(a, rank: int, world: int, n_local: int):
                 managers=0, dp_mode="node", calls=len(llm.calls) if hasattr(llm, "calls") else 0, prompt_tokens=0,
                 completion_tokens=0, async_steps=False, host_phases={}, req_lat={}, memory=None, node_load=None,
                 buckets={}, cpu_rank=True)
+
+
+def _result_record(rank: int, ci: int, doc: str, r) -> dict:
+    """One client's latest timed task as --dump-outputs keeps it (see dump_outputs)."""
+    md = r.metadata or {}
+    steps = r.output if isinstance(r.output, list) else []
+    results = [s.get("result") for s in steps if isinstance(s, dict)]
+    return {"rank": rank, "client": ci, "success": bool(r.success), "document": doc,
+            "control": [int(md.get("iterations") or 0), len(steps),
+                        sum(1 for x in results if isinstance(x, dict) and x.get("status") == "success"),
+                        int(bool((md.get("analysis") or {}).get("can_execute"))),
+                        len((md.get("tools_used") or {}).get("selected_tools") or []),
+                        int(bool((md.get("evaluation") or {}).get("success")))],
+            "tools": json.dumps(results, sort_keys=True, default=str),
+            "replies": {"output": r.output, "error": r.error,
+                        **{k: md.get(k) for k in ("analysis", "tools_used", "evaluation")}}}
+
+
+def _byte_rows(np, texts: list):
+    """UTF-8 byte values of each text, one row each, padded with -1 to the longest."""
+    raws = [t.encode("utf-8") for t in texts]
+    out = np.full((len(raws), max([len(x) for x in raws] + [1])), -1.0, dtype=np.float32)
+    for i, raw in enumerate(raws):
+        out[i, :len(raw)] = np.frombuffer(raw, dtype=np.uint8)
+    return out
+
+
+def dump_outputs(path: str, records: list) -> dict:
+    """--dump-outputs DIR: each client's task of the last timed step, one row per client in
+    (rank, client) order. The arrays hold what is the same in every run with the same
+    arguments, so that two builds can be compared array for array:
+
+      task_document_bytes.npy      float32 [clients, L]  the document the task carried (the input the
+                                                         other rows belong to; follows --seed)
+      task_success.npy             float32 [clients]     1.0 where the TaskResult reports success
+      task_control.npy             float64 [clients, 8]  rank, client, agent iterations, executed steps,
+                                                         steps whose tool succeeded, analysis.can_execute,
+                                                         tools selected, evaluation.success
+      task_tool_results_bytes.npy  float32 [clients, M]  the executed steps' tool results, canonical JSON
+
+    (byte rows: UTF-8 values padded with -1 to the longest row, nothing is cut). Under the
+    `fixed` policy the control fields and tool results are pinned by the caller, so these rows
+    show that the control flow ran, not what the model wrote. What the model wrote -- every
+    reply the caller receives in the TaskResult -- goes to DIR/task_replies.jsonl, one line per
+    client, and is NOT the same from run to run: the free-text slots are sampled at temperature
+    0.7 from a continuous batch whose composition follows the requests' arrival times, a step
+    of another size runs other GEMM kernels with other bf16 rounding, and with random-init
+    weights (near-flat logits) that moves sampled tokens, after which the later prompts of the
+    task differ too (tests/test_engine_gpu.py::test_sampling_batch_invariance states the
+    limit). Two runs of one build agree in the replies' JSON structure and pinned fields and
+    differ in nearly all sampled text; compare that file with this in mind."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    records = sorted(records, key=lambda d: (d["rank"], d["client"]))
+    arrays = {
+        "task_document_bytes": _byte_rows(np, [d["document"] for d in records]),
+        "task_success": np.array([1.0 if d["success"] else 0.0 for d in records], dtype=np.float32),
+        "task_control": np.array([(d["rank"], d["client"], *d["control"]) for d in records],
+                                 dtype=np.float64).reshape(len(records), 8),
+        "task_tool_results_bytes": _byte_rows(np, [d["tools"] for d in records]),
+    }
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+    with open(os.path.join(path, "task_replies.jsonl"), "w") as f:
+        for d in records:
+            f.write(json.dumps({"rank": d["rank"], "client": d["client"], "document": d["document"],
+                                **d["replies"]}, sort_keys=True, default=str) + "\n")
+    return {name: list(arr.shape) for name, arr in arrays.items()}
 
 
 def _device_identity(device) -> dict:
@@ -633,6 +718,9 @@ def main():
         lat0 = gathered[0]["req_lat"]  # rank 0's request timings (per-GPU engines are alike)
         calls = max(1, tot("calls"))
         value = tasks / dt if dt > 0 else 0.0
+        dumped = None
+        if a.dump_outputs:
+            dumped = dump_outputs(a.dump_outputs, [d for g in gathered for d in g.get("last_results", [])])
         # scale-run evidence: physical GPUs the ranks actually used (a --share-gpu or hybrid
         # rehearsal of N ranks on one card reports n_gpus 1), the process group RCCL / gloo saw
         phys = sorted({g["device"]["physical"] for g in everyone if g["device"]["physical"]})
@@ -720,6 +808,9 @@ def main():
             "node_load": gathered[0]["node_load"],
             # bench --tp: the start-up all-reduce check and latencies (BENCHMARKS.md, DP x TP cost model)
             "tp_selftest": getattr(a, "_tp_selftest", None),
+            "seed": a.seed,
+            "full": bool(a.full),
+            "dumped_outputs": dumped,
             "notes": "BASELINE.md publishes no number for this config (vs_baseline null); the reference's "
                      "structural bound with a remote LLM is ~0.8 tasks/s per LLMHandler (BASELINE.md §2).",
         }

@@ -62,6 +62,95 @@ def test_bench_multi_rank_json_contract(tmp_path, n, launcher, rehearsal):
     assert d["devices"] == ["cpu"] * n
 
 
+def _load_bench():
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_bench_dump_outputs_full_and_step_count(tmp_path):
+    """One rank (tiny model on CPU) with `--full --dump-outputs DIR`: --steps sets the number
+    of timed steps (every worker completes exactly that many timed tasks), ms_per_step is the
+    timed region over the steps, and DIR holds the last timed step's tasks, one row per client:
+    documents, success flags, control fields and tool results as float .npy arrays within the
+    64 MB limit, and the replies the caller received as task_replies.jsonl."""
+    import numpy as np
+
+    env = dict(os.environ, CUDA_VISIBLE_DEVICES="")
+    env.pop("WORLD_SIZE", None)
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--cpu", "--steps", "2", "--warmup", "1",
+           "--workers", "3", "--doc-words", "20", "--full", "--dump-outputs", str(out)]
+    p = subprocess.run(cmd, cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["tasks"] == 2 * 3
+    assert d["full"] is True and d["seed"] == _load_bench().parse([]).seed
+    assert abs(d["ms_per_step"] - 1000.0 * d["seconds"] / 2) <= 0.01 * d["ms_per_step"] + 0.01
+    assert d["unit"] == "tasks/s" and d["higher_is_better"] is True and d["dtype"] == "bf16"
+    files = sorted(f for f in os.listdir(out))
+    assert files == ["task_control.npy", "task_document_bytes.npy", "task_replies.jsonl", "task_success.npy",
+                     "task_tool_results_bytes.npy"]
+    arrs = {f[:-4]: np.load(out / f) for f in files if f.endswith(".npy")}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+    assert sum(a.nbytes for a in arrs.values()) <= 64 * 2**20
+    assert d["dumped_outputs"] == {k: list(a.shape) for k, a in arrs.items()}
+    assert arrs["task_success"].tolist() == [1.0, 1.0, 1.0]  # a failed task ends the run
+    # one row per client, in order; the fixed policy's control flow: one iteration, one executed
+    # echo step that succeeded, can_execute, one selected tool, a success verdict
+    assert arrs["task_control"].tolist() == [[0.0, c, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0] for c in (0.0, 1.0, 2.0)]
+    for row in arrs["task_tool_results_bytes"]:  # whole JSON, nothing cut
+        assert json.loads(_row_text(row)) == [{"output": {"echo": {}}, "status": "success"}]
+    docs = [_row_text(row) for row in arrs["task_document_bytes"]]
+    words = set(_load_bench()._WORDS)
+    assert len(set(docs)) == 3 and all(len(t.split()) == 20 and set(t.split()) <= words for t in docs)
+    # the model's replies, as the caller received them, beside the arrays: one line per client
+    replies = [json.loads(ln) for ln in open(out / "task_replies.jsonl")]
+    assert [r["client"] for r in replies] == [0, 1, 2] and [r["document"] for r in replies] == docs
+    for r in replies:
+        assert r["evaluation"]["success"] is True and r["analysis"]["can_execute"] is True
+        assert r["output"][0]["step"]["tool"] == "echo"
+
+
+def _row_text(row) -> str:
+    import numpy as np
+
+    return bytes(row[row >= 0].astype(np.uint8)).decode("utf-8")
+
+
+def test_bench_inputs_repeat_from_run_to_run(tmp_path):
+    """The documents a run submits follow --seed and nothing else: two runs with the same
+    arguments dump the same documents (and the same arrays altogether), a run with another
+    seed dumps other documents. Three one-step runs of the tiny CPU model, side by side."""
+    import numpy as np
+
+    env = dict(os.environ, CUDA_VISIBLE_DEVICES="")
+    env.pop("WORLD_SIZE", None)
+    runs = {"a": [], "b": [], "c": ["--seed", "7"]}
+    procs = {k: subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--cpu", "--steps", "1",
+                                  "--warmup", "0", "--workers", "2", "--doc-words", "20",
+                                  "--dump-outputs", str(tmp_path / k), *extra],
+                                 cwd=str(tmp_path), env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+             for k, extra in runs.items()}
+    lines = {}
+    for k, p in procs.items():
+        out, err = p.communicate(timeout=900)
+        assert p.returncode == 0, err[-3000:]
+        lines[k] = json.loads([ln for ln in out.splitlines() if ln.startswith("{")][0])
+    assert lines["a"]["seed"] == lines["b"]["seed"] != lines["c"]["seed"] == 7
+    names = sorted(f for f in os.listdir(tmp_path / "a") if f.endswith(".npy"))
+    arrs = {k: {f: np.load(tmp_path / k / f) for f in names} for k in runs}
+    for f in names:
+        assert arrs["a"][f].shape == arrs["b"][f].shape and (arrs["a"][f] == arrs["b"][f]).all(), f
+    docs = {k: [_row_text(r) for r in arrs[k]["task_document_bytes.npy"]] for k in runs}
+    assert docs["a"] == docs["b"] and not set(docs["a"]) & set(docs["c"])
+
+
 def test_bench_device_identity_counts_physical_cards():
     """n_gpus is the number of DISTINCT physical cards over the ranks (unit check of the
     identity helper on fake device properties)."""

@@ -1,6 +1,6 @@
 """The hierarchical PDF example end to end on CPU, plus the PDF
-text extractor on generated files and on the reference's sample PDF (read as
-plain bytes; skipped when the reference tree is absent)."""
+text extractor on generated files and on the reference's sample PDF (a stored
+copy under tests/golden, read as plain bytes)."""
 import asyncio
 import os
 
@@ -8,7 +8,7 @@ import pytest
 
 from pilottai_amd.tools import pdf
 
-REF_SAMPLE = "/root/reference/docs/examples/pdf_processing/sample_doc.pdf"
+REF_SAMPLE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sample_doc.pdf")
 
 
 def test_pdf_roundtrip(tmp_path):
@@ -23,7 +23,6 @@ def test_pdf_roundtrip(tmp_path):
     assert pdf.extract_text(open(p, "rb").read()) == ["plain"]
 
 
-@pytest.mark.skipif(not os.path.exists(REF_SAMPLE), reason="reference sample not present")
 def test_reference_sample_pdf_cid_font():
     # Type0 / Identity-H font with a ToUnicode CMap, glyph-by-glyph positioning
     assert pdf.extract_text(open(REF_SAMPLE, "rb").read()) == ["What is the capital of india?"]
