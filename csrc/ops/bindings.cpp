@@ -26,6 +26,11 @@ int pa_sample(int* out_tokens, float* out_keys, float* workspace, const void* lo
               int V, int ld, int vocab_offset, const float* temperature, const int* mask_class,
               const uint32_t* class_masks, int mask_words, const int64_t* seeds,
               const int* offsets, const int* forced, const float* tau, hipStream_t st);
+int pa_logprob_workspace_floats(int rows, int V);
+int pa_token_logprobs(float* out_lp, int out_stride, int* top_ids, float* top_lp, int top_stride, float* workspace,
+                      const void* logits, int rows, int V, int ld, const int* tokens, const int* lp_n,
+                      const int* forced, const int* mask_class, const uint32_t* class_masks, int mask_words,
+                      hipStream_t st);
 int pa_tp_topkp_phase(int phase, float* tau, float* ws, const void* logits, int rows, int v_local, int ld,
                       int vocab_offset, int V, const float* temperature, const int* top_k, const float* top_p,
                       const int* mask_class, const uint32_t* class_masks, int mask_words, hipStream_t st);
@@ -652,6 +657,55 @@ void sample(at::Tensor out_tokens, c10::optional<at::Tensor> out_keys, at::Tenso
            "sample");
 }
 
+int64_t logprob_workspace_floats(int64_t rows, int64_t V) {
+  return pa_logprob_workspace_floats(rows, V);
+}
+
+// Per-token log-probabilities behind sample() (sampling.hip logprob_*_kernel). out_lp [rows],
+// top_ids / top_lp [rows, 20]: unit inner stride, any row stride (columns of one record buffer).
+void token_logprobs(at::Tensor out_lp, at::Tensor top_ids, at::Tensor top_lp, at::Tensor workspace,
+                    at::Tensor logits, at::Tensor tokens, at::Tensor lp_n, at::Tensor forced,
+                    at::Tensor mask_class, at::Tensor class_masks) {
+  check_gpu(workspace, "workspace"); check_gpu(tokens, "tokens"); check_gpu(lp_n, "lp_n");
+  check_gpu(forced, "forced"); check_gpu(mask_class, "mask_class"); check_gpu(class_masks, "class_masks");
+  TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.stride(1) == 1,
+              "logits must be a 2-D GPU tensor with unit inner stride");
+  check_dtype(logits, at::kBFloat16, "logits"); check_dtype(workspace, at::kFloat, "workspace");
+  check_dtype(tokens, at::kInt, "tokens"); check_dtype(lp_n, at::kInt, "lp_n");
+  check_dtype(forced, at::kInt, "forced"); check_dtype(mask_class, at::kInt, "mask_class");
+  check_dtype(class_masks, at::kInt, "class_masks");
+  check_dtype(out_lp, at::kFloat, "out_lp"); check_dtype(top_ids, at::kInt, "top_ids");
+  check_dtype(top_lp, at::kFloat, "top_lp");
+  const int64_t rows = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(out_lp.is_cuda() && out_lp.dim() == 1 && out_lp.size(0) >= rows, "out_lp: [rows] GPU tensor");
+  TORCH_CHECK(top_ids.is_cuda() && top_ids.dim() == 2 && top_ids.size(0) >= rows && top_ids.size(1) == 20 &&
+                  top_ids.stride(1) == 1,
+              "top_ids: [rows, 20] GPU tensor with unit inner stride");
+  TORCH_CHECK(top_lp.is_cuda() && top_lp.dim() == 2 && top_lp.size(0) >= rows && top_lp.size(1) == 20 &&
+                  top_lp.stride(1) == 1 && top_lp.stride(0) == top_ids.stride(0),
+              "top_lp: [rows, 20] GPU tensor laid out like top_ids");
+  TORCH_CHECK(rows == 0 || (out_lp.stride(0) >= 1 && top_ids.stride(0) >= 20), "logprob outputs overlap");
+  TORCH_CHECK(tokens.numel() >= rows && lp_n.numel() >= rows && forced.numel() >= rows &&
+                  mask_class.numel() >= rows,
+              "per-row logprob parameter tensors too short");
+  const int64_t ld = rows > 1 ? logits.stride(0) : V;  // a one-row view's stride is arbitrary
+  TORCH_CHECK(V > 0 && V % 8 == 0 && ld % 8 == 0 && ld >= V, "logits: V and the row stride must be multiples of 8");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(logits.data_ptr()) & 15) == 0,
+              "logits must start 16-byte aligned (rows are read as 16-byte vectors)");
+  TORCH_CHECK(V <= 64 * 4096, "token_logprobs supports vocabularies up to 262144 entries");
+  TORCH_CHECK(workspace.numel() >= pa_logprob_workspace_floats(rows, V), "logprob workspace too small");
+  TORCH_CHECK(class_masks.dim() == 2 && class_masks.is_contiguous(), "class_masks must be [classes, words]");
+  TORCH_CHECK(class_masks.size(1) * 32 >= V, "class_masks too narrow for vocab");
+  check_rc(pa_token_logprobs(out_lp.data_ptr<float>(), (int)out_lp.stride(0), top_ids.data_ptr<int>(),
+                             top_lp.data_ptr<float>(), (int)top_ids.stride(0), workspace.data_ptr<float>(),
+                             logits.data_ptr(), (int)rows, (int)V, (int)ld,
+                             tokens.data_ptr<int>(), lp_n.data_ptr<int>(), forced.data_ptr<int>(),
+                             mask_class.data_ptr<int>(),
+                             reinterpret_cast<const uint32_t*>(class_masks.data_ptr<int>()),
+                             (int)class_masks.size(1), cur_stream()),
+             "token_logprobs");
+}
+
 int64_t cosine_topk_workspace_bytes(int64_t Q, int64_t N, int64_t K) {
   return pa_cosine_topk_workspace_bytes(Q, N, K);
 }
@@ -993,6 +1047,10 @@ PYBIND11_MODULE(_C, m) {
         py::arg("class_masks"), py::arg("seeds"), py::arg("offsets"), py::arg("forced"),
         py::arg("tau") = py::none());
   m.def("topkp_threshold", &topkp_threshold);
+  m.def("logprob_workspace_floats", &logprob_workspace_floats);
+  m.def("token_logprobs", &token_logprobs, py::arg("out_lp"), py::arg("top_ids"), py::arg("top_lp"),
+        py::arg("workspace"), py::arg("logits"), py::arg("tokens"), py::arg("lp_n"), py::arg("forced"),
+        py::arg("mask_class"), py::arg("class_masks"));
   m.def("tp_topkp_phase", &tp_topkp_phase);
   m.def("cosine_topk_workspace_bytes", &cosine_topk_workspace_bytes);
   m.def("cosine_topk", &cosine_topk);

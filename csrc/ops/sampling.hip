@@ -434,6 +434,259 @@ extern "C" int pa_sample(int* out_tokens, float* out_keys, float* workspace, con
   return (int)hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// Per-token log-probabilities. The sampler never normalises (Gumbel-max), so this is a pass of
+// its own over the logits, run behind pa_sample on the same stream: the distribution is
+// softmax(logits) over the tokens the row's grammar mask allows, at temperature 1 (independent
+// of the request's temperature / top-k / top-p / seed), natural log.
+//   logprob_chunk_kernel  grid (nchunk, rows), 256 threads: the chunk's 4096 entries are read
+//       once as 16-byte vectors into registers (masked entries become -inf); fp32 (max,
+//       sum exp(x - max)) of the chunk; each wave extracts its top-n by repeated wave argmax over
+//       the register values (larger logit first, equal logits by smaller id: one unsigned max
+//       of the bf16 order key packed above the inverted index in the chunk), wave 0 merges the
+//       four sorted lists into the chunk's top-n.
+//   logprob_merge_kernel  one wave per row: combines the chunk normalisers into the row's
+//       log-sum-exp, merges the chunks' sorted lists (lane c owns chunk c's list) into the
+//       row's top-n, reads the chosen token's logit, writes the outputs.
+// Two plain launches, no flags or atomics between workgroups. Rows with lp_n < 0 are skipped
+// (nothing read, nothing written); rows with forced >= 0 write (0.0, [(forced, 0.0)]) without
+// reading logits. A row whose mask allows nothing gets -inf and an empty list. Entries past
+// the end of a list are (id -1, -inf). Logits of -inf are never listed.
+// This file is compiled with -ffast-math (no-infs): inside the kernels a masked entry is the
+// finite LP_NEG, every test is a finite or an integer comparison, and the -inf of the outputs
+// is stored as its bit pattern.
+namespace pa {
+
+constexpr float LP_NEG = -3.0e38f;      // masked / absent entry (below every bf16 logit in use)
+constexpr float LP_LIVE = -1.0e38f;     // x > LP_LIVE: a real logit
+constexpr int LP_NEG_INF_BITS = (int)0xff800000u;
+__device__ __forceinline__ void store_neg_inf(float* p) { *reinterpret_cast<int*>(p) = LP_NEG_INF_BITS; }
+
+constexpr int LP_MAX = 20;              // alternatives per token (the OpenAI API's limit)
+constexpr int LP_WS = 2 + 2 * LP_MAX;   // floats per (row, chunk): max, sum, 20 logits, 20 ids
+constexpr int LP_MAX_CHUNKS = 64;       // one lane of the merge wave per chunk (V <= 262144)
+
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o, 64));
+  return v;
+}
+
+__device__ __forceinline__ KeyIdx wave_best(KeyIdx b) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    KeyIdx other{__shfl_xor(b.k, o, 64), __shfl_xor(b.i, o, 64)};
+    b = better(b, other);
+  }
+  return b;
+}
+
+// Merge sorted (logit, id) lists into the first n entries of their union, one list per owning
+// lane (`owner`; ids are unique over all lists; a list ends at id < 0 or after `len` entries).
+// Every lane of the wave calls it; lane 0 writes out_k[k] = logit - sub, out_i[k] = id, and
+// (-inf, -1) from the end of the merged list up to `pad` entries.
+__device__ __forceinline__ void lp_merge_lists(const float* lk, const int* li, int len, bool owner, int n,
+                                               float* out_k, int* out_i, int pad, float sub) {
+  const int lane = threadIdx.x & 63;
+  int p = 0, k = 0;
+  for (; k < n; ++k) {
+    KeyIdx h{LP_NEG, 0x7fffffff};
+    if (owner && p < len) {
+      const int id = li[p];
+      if (id >= 0) h = KeyIdx{lk[p], id};
+    }
+    const KeyIdx w = wave_best(h);
+    if (w.i == 0x7fffffff) break;  // every list is exhausted (wave-uniform)
+    if (h.i == w.i) ++p;
+    if (lane == 0) {
+      out_k[k] = w.k - sub;
+      out_i[k] = w.i;
+    }
+  }
+  if (lane == 0)
+    for (; k < pad; ++k) {
+      store_neg_inf(out_k + k);
+      out_i[k] = -1;
+    }
+}
+
+__global__ __launch_bounds__(256) void logprob_chunk_kernel(
+    float* __restrict__ ws, const bf16* __restrict__ logits, int V, int ld, const int* __restrict__ lp_n,
+    const int* __restrict__ forced, const int* __restrict__ mask_class,
+    const uint32_t* __restrict__ class_masks, int mask_words, int nchunk) {
+  const int row = blockIdx.y, chunk = blockIdx.x;
+  const int n_req = lp_n[row];
+  if (n_req < 0 || forced[row] >= 0) return;  // the whole workgroup
+  const int n = min(n_req, LP_MAX);
+  const int mc = mask_class[row];
+  const bf16* lr = logits + (size_t)row * ld;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int base = chunk * SMP_CHUNK + threadIdx.x * 8;
+  // v: the logit (LP_NEG when masked); key: its rank inside the chunk as one unsigned number,
+  // the bf16 order key above (4095 - index in the chunk), so one unsigned max is "larger logit,
+  // then smaller id"; 0 = masked or retired
+  float v[16];
+  uint32_t key[16];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int i0 = base + h * 2048;
+    if (i0 < V) {  // V % 8 == 0: a vector is inside the row or past it as a whole
+      const u32x4 raw = *reinterpret_cast<const u32x4*>(lr + i0);
+      uint32_t bits = 0xffffffffu;
+      if (mc >= 0) bits = class_masks[(size_t)mc * mask_words + (i0 >> 5)] >> (i0 & 31);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const uint32_t b16 = (raw[j >> 1] >> ((j & 1) * 16)) & 0xffffu;
+        const float x = __uint_as_float(b16 << 16);
+        const bool live = ((bits >> j) & 1u) && x > LP_LIVE;  // a logit of -inf counts as masked
+        const uint32_t local = (uint32_t)(threadIdx.x * 8 + h * 2048 + j);
+        v[h * 8 + j] = live ? x : LP_NEG;
+        key[h * 8 + j] = live ? ((bf16_order_key((uint16_t)b16) << 12) | (4095u - local)) : 0u;
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        v[h * 8 + j] = LP_NEG;
+        key[h * 8 + j] = 0u;
+      }
+    }
+  }
+  __shared__ float s_red[8];
+  __shared__ uint32_t s_key[4][LP_MAX];
+  // the chunk's normaliser: max, then sum exp(x - max)
+  float m = v[0];
+#pragma unroll
+  for (int j = 1; j < 16; ++j) m = fmaxf(m, v[j]);
+  m = wave_max(m);
+  if (lane == 0) s_red[wid] = m;
+  __syncthreads();
+  m = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
+  float s = 0.f;
+  if (m > LP_LIVE) {
+#pragma unroll
+    for (int j = 0; j < 16; ++j) s += v[j] > LP_LIVE ? __expf(v[j] - m) : 0.f;
+  }
+  s = wave_sum(s);
+  if (lane == 0) s_red[4 + wid] = s;
+  __syncthreads();
+  float* w = ws + ((size_t)row * nchunk + chunk) * LP_WS;
+  if (threadIdx.x == 0) {
+    w[0] = m;
+    w[1] = (s_red[4] + s_red[5]) + (s_red[6] + s_red[7]);
+  }
+  if (n == 0) return;
+  // this wave's top-n: n rounds of (thread best over its registers, wave argmax, the owner
+  // retires the winner); keys are unique inside a chunk
+  int it = 0;
+  for (; it < n; ++it) {
+    uint32_t b = key[0];
+#pragma unroll
+    for (int j = 1; j < 16; ++j) b = max(b, key[j]);
+    const uint32_t win = wave_max_u32(b);
+    if (win == 0u) break;  // nothing allowed is left in this wave (wave-uniform)
+    if (lane == 0) s_key[wid][it] = win;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) key[j] = key[j] == win ? 0u : key[j];
+  }
+  if (lane == 0)
+    for (; it < n; ++it) s_key[wid][it] = 0u;
+  __syncthreads();
+  // wave 0 merges the four sorted lists (lane l < 4 holds the head of wave l's list)
+  if (wid != 0) return;
+  float* out_k = w + 2;
+  int* out_i = reinterpret_cast<int*>(w + 2 + LP_MAX);
+  int p = 0, k = 0;
+  for (; k < n; ++k) {
+    const uint32_t h = (lane < 4 && p < n) ? s_key[lane & 3][p] : 0u;
+    const uint32_t win = wave_max_u32(h);
+    if (win == 0u) break;  // wave-uniform
+    if (h == win) ++p;
+    if (lane == 0) {
+      out_k[k] = order_key_value(win >> 12);
+      out_i[k] = chunk * SMP_CHUNK + 4095 - (int)(win & 4095u);
+    }
+  }
+  if (lane == 0)
+    for (; k < n; ++k) {
+      store_neg_inf(out_k + k);
+      out_i[k] = -1;
+    }
+}
+
+__global__ __launch_bounds__(64) void logprob_merge_kernel(
+    float* __restrict__ out_lp, int out_stride, int* __restrict__ top_ids, float* __restrict__ top_lp,
+    int top_stride, const float* __restrict__ ws, const bf16* __restrict__ logits, int V, int ld,
+    const int* __restrict__ tokens, const int* __restrict__ lp_n, const int* __restrict__ forced,
+    const int* __restrict__ mask_class, const uint32_t* __restrict__ class_masks, int mask_words, int nchunk) {
+  const int row = blockIdx.x, lane = threadIdx.x;
+  const int n_req = lp_n[row];
+  if (n_req < 0) return;
+  const int n = min(n_req, LP_MAX);
+  int* ti = top_ids + (size_t)row * top_stride;
+  float* tl = top_lp + (size_t)row * top_stride;
+  float* ol = out_lp + (size_t)row * out_stride;
+  const int f = forced[row];
+  if (f >= 0) {  // structural text: the grammar left no choice
+    if (lane < LP_MAX) {
+      const bool first = lane == 0 && n > 0;
+      ti[lane] = first ? f : -1;
+      reinterpret_cast<int*>(tl)[lane] = first ? 0 : LP_NEG_INF_BITS;
+    }
+    if (lane == 0) *ol = 0.f;
+    return;
+  }
+  const float* w = ws + ((size_t)row * nchunk + min(lane, nchunk - 1)) * LP_WS;
+  const bool owner = lane < nchunk;
+  const float m = owner ? w[0] : LP_NEG;
+  const float M = wave_max(m);
+  if (!(M > LP_LIVE)) {  // the mask allows nothing (the sampler emitted token 0)
+    if (lane < LP_MAX) {
+      ti[lane] = -1;
+      store_neg_inf(tl + lane);
+    }
+    if (lane == 0) store_neg_inf(ol);
+    return;
+  }
+  const float S = wave_sum(m > LP_LIVE ? w[1] * __expf(m - M) : 0.f);
+  const float lse = M + logf(S);
+  if (lane == 0) {
+    const int tok = tokens[row];
+    const int mc = mask_class[row];
+    store_neg_inf(ol);  // a token the mask does not allow (or a logit of -inf)
+    if (tok >= 0 && tok < V &&
+        (mc < 0 || ((class_masks[(size_t)mc * mask_words + (tok >> 5)] >> (tok & 31)) & 1u))) {
+      const float x = bf2f(logits[(size_t)row * ld + tok]);
+      if (x > LP_LIVE) *ol = x - lse;
+    }
+  }
+  lp_merge_lists(w + 2, reinterpret_cast<const int*>(w + 2 + LP_MAX), n, owner, n, tl, ti, LP_MAX, lse);
+}
+
+}  // namespace pa
+
+extern "C" int pa_logprob_workspace_floats(int rows, int V) {
+  const int nchunk = (V + pa::SMP_CHUNK - 1) / pa::SMP_CHUNK;
+  return rows * nchunk * pa::LP_WS;
+}
+
+// out_lp[row * out_stride]; top_ids / top_lp [row * top_stride + 0..19] (the three may be
+// columns of one record buffer). workspace: pa_logprob_workspace_floats(rows, V) floats.
+extern "C" int pa_token_logprobs(float* out_lp, int out_stride, int* top_ids, float* top_lp, int top_stride,
+                                 float* workspace, const void* logits, int rows, int V, int ld,
+                                 const int* tokens, const int* lp_n, const int* forced, const int* mask_class,
+                                 const uint32_t* class_masks, int mask_words, hipStream_t st) {
+  if (rows <= 0) return 0;
+  if (V <= 0 || V % 8 != 0 || ld % 8 != 0 || ld < V || top_stride < pa::LP_MAX || out_stride < 1) return -1;
+  const int nchunk = (V + pa::SMP_CHUNK - 1) / pa::SMP_CHUNK;
+  if (nchunk > pa::LP_MAX_CHUNKS) return -1;
+  hipLaunchKernelGGL(pa::logprob_chunk_kernel, dim3(nchunk, rows), dim3(256), 0, st, workspace,
+                     (const pa::bf16*)logits, V, ld, lp_n, forced, mask_class, class_masks, mask_words, nchunk);
+  hipLaunchKernelGGL(pa::logprob_merge_kernel, dim3(rows), dim3(64), 0, st, out_lp, out_stride, top_ids, top_lp,
+                     top_stride, workspace, (const pa::bf16*)logits, V, ld, tokens, lp_n, forced, mask_class,
+                     class_masks, mask_words, nchunk);
+  return (int)hipGetLastError();
+}
+
 // Pipelined engine steps (engine.py, async_steps): a row whose previous token is still
 // being sampled by the step in flight enters the next step with input id -(r + 1), r =
 // its sampling row there. This runs first in the next step's graph, after the previous

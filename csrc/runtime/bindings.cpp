@@ -34,9 +34,22 @@ std::unique_ptr<Grammar> make_grammar(const py::object& segs) {
 
 py::list outputs_to_py(const std::vector<SeqOutput>& outs) {
   py::list l;
-  for (const auto& o : outs)
+  for (const auto& o : outs) {
+    // last element: None, or per generated token (logprob, [(token id, logprob) x <= n])
+    py::object lps = py::none();
+    if (o.logprobs >= 0) {
+      py::list recs;
+      for (const LogprobRecord& r : o.lp_records) {
+        py::list top;
+        for (int32_t i = 0; i < o.logprobs && i < LOGPROB_TOP && r.ids[i] >= 0; ++i)
+          top.append(py::make_tuple(r.ids[i], (double)r.lps[i]));
+        recs.append(py::make_tuple((double)r.lp, top));
+      }
+      lps = recs;
+    }
     l.append(py::make_tuple(o.id, o.tokens, o.finish_reason, o.prompt_len, o.cached_prompt_tokens,
-                            o.num_sampled, o.num_forced, o.t_first_token, o.t_finish, o.embed_slot));
+                            o.num_sampled, o.num_forced, o.t_first_token, o.t_finish, o.embed_slot, lps));
+  }
   return l;
 }
 
@@ -183,6 +196,7 @@ PYBIND11_MODULE(_runtime, m) {
         d["top_k"] = L.top_k; d["top_p"] = L.top_p;
         d["items"] = L.items; d["n_items"] = L.n_items; d["part_size"] = L.part_size;
         d["counts"] = L.counts; d["block_table"] = L.block_table; d["embed_rows"] = L.embed_rows;
+        d["lp_n"] = L.lp_n;
         d["total"] = L.total;
         return d;
       })
@@ -190,26 +204,31 @@ PYBIND11_MODULE(_runtime, m) {
            [](Scheduler& s, int64_t id, const std::vector<int32_t>& prompt, float temperature,
               int32_t max_tokens, int64_t seed, bool ignore_eos,
               const std::vector<int32_t>& stop_ids, const py::object& grammar, int32_t top_k,
-              float top_p, bool embed, bool embed_last) {
+              float top_p, bool embed, bool embed_last, int32_t logprobs) {
              s.add_request(id, prompt, temperature, max_tokens, seed, ignore_eos, stop_ids,
-                           make_grammar(grammar), top_k, top_p, embed, embed_last);
+                           make_grammar(grammar), top_k, top_p, embed, embed_last, logprobs);
            },
            py::arg("id"), py::arg("prompt"), py::arg("temperature"), py::arg("max_tokens"),
            py::arg("seed"), py::arg("ignore_eos"), py::arg("stop_ids"), py::arg("grammar"),
            py::arg("top_k") = 0, py::arg("top_p") = 1.0f, py::arg("embed") = false,
-           py::arg("embed_last") = false)
+           py::arg("embed_last") = false, py::arg("logprobs") = -1)
       .def("schedule", [](Scheduler& s, uintptr_t buf) {
         py::gil_scoped_release nogil;
         return s.schedule(reinterpret_cast<int32_t*>(buf));
       })
-      .def("commit", [](Scheduler& s, uintptr_t sampled, int32_t n) {
+      // logprobs: address of the step's LogprobRecord array (41 32-bit words per sampling row:
+      // logprob, 20 ids, 20 logprobs), 0 = the step computed none
+      .def("commit", [](Scheduler& s, uintptr_t sampled, int32_t n, uintptr_t logprobs) {
         std::vector<SeqOutput> outs;
         {
           py::gil_scoped_release nogil;
-          outs = s.commit(reinterpret_cast<const int32_t*>(sampled), n);
+          outs = s.commit(reinterpret_cast<const int32_t*>(sampled), n,
+                          reinterpret_cast<const LogprobRecord*>(logprobs));
         }
         return outputs_to_py(outs);
-      })
+      }, py::arg("sampled"), py::arg("n"), py::arg("logprobs") = 0)
+      .def_property_readonly_static("LOGPROB_RECORD_WORDS",
+                                    [](const py::object&) { return (int)(sizeof(LogprobRecord) / 4); })
       .def("abort", &Scheduler::abort)
       .def("take_embed_resets", &Scheduler::take_embed_resets)
       .def("num_free_embed_rows", &Scheduler::num_free_embed_rows)

@@ -2,6 +2,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstring>
 #include <stdexcept>
 #include <unordered_set>
@@ -14,6 +15,21 @@ double now_seconds() {
 }
 
 static int32_t align4(int32_t x) { return (x + 3) & ~3; }
+
+// the record of a token the grammar left no choice for: probability 1 among the allowed tokens
+static LogprobRecord forced_record(int32_t tok, int32_t n) {
+  LogprobRecord r;
+  r.lp = 0.f;
+  for (int32_t i = 0; i < LOGPROB_TOP; ++i) {
+    r.ids[i] = -1;
+    r.lps[i] = -INFINITY;
+  }
+  if (n > 0) {
+    r.ids[0] = tok;
+    r.lps[0] = 0.f;
+  }
+  return r;
+}
 
 Scheduler::Scheduler(const SchedulerConfig& cfg)
     : cfg_(cfg), bm_(cfg.num_blocks, cfg.block_size, cfg.prefix_caching) {
@@ -30,7 +46,7 @@ Scheduler::Scheduler(const SchedulerConfig& cfg)
     o = align4(o + n);
     return at;
   };
-  L.counts = take(8);
+  L.counts = take(12);
   L.n_items = take(1);
   L.part_size = take(1);
   L.input_ids = take(L.max_tokens);
@@ -47,6 +63,7 @@ Scheduler::Scheduler(const SchedulerConfig& cfg)
   L.top_k = take(L.max_seqs);
   L.top_p = take(L.max_seqs);
   L.seeds = take(2 * L.max_seqs);
+  L.lp_n = take(L.max_seqs);
   L.items = take(4 * L.max_items);
   L.block_table = take(L.max_seqs * L.max_blocks);
   L.embed_rows = take(L.max_tokens);
@@ -57,7 +74,7 @@ Scheduler::Scheduler(const SchedulerConfig& cfg)
 void Scheduler::add_request(int64_t id, std::vector<int32_t> prompt, float temperature,
                             int32_t max_tokens, int64_t seed, bool ignore_eos,
                             std::vector<int32_t> stop_ids, std::unique_ptr<Grammar> grammar,
-                            int32_t top_k, float top_p, bool embed, bool embed_last) {
+                            int32_t top_k, float top_p, bool embed, bool embed_last, int32_t logprobs) {
   auto s = std::make_unique<Sequence>();
   s->id = id;
   if ((int32_t)prompt.size() >= cfg_.max_model_len)
@@ -75,6 +92,7 @@ void Scheduler::add_request(int64_t id, std::vector<int32_t> prompt, float tempe
   s->grammar = embed ? nullptr : std::move(grammar);
   s->embed = embed;
   s->embed_last = embed && embed_last;
+  s->logprobs = embed ? -1 : std::min(logprobs, LOGPROB_TOP);
   s->arrival = arrival_counter_++;
   // a grammar that starts with forced text (e.g. '{"key": ') is jump-forwarded into the prompt
   if (s->grammar) {
@@ -82,6 +100,9 @@ void Scheduler::add_request(int64_t id, std::vector<int32_t> prompt, float tempe
     const int32_t k = s->grammar->take_forced_run(s->tokens, std::min(room, s->max_tokens - 1));
     s->num_generated += k;
     s->num_forced += k;
+    if (s->logprobs >= 0)
+      for (int32_t j = 0; j < k; ++j)
+        s->lp_records.push_back(forced_record(s->tokens[s->prompt_len + j], s->logprobs));
   }
   Sequence* raw = s.get();
   seqs_.emplace(id, std::move(s));
@@ -317,6 +338,8 @@ int32_t Scheduler::schedule(int32_t* buf) {
   int32_t* off = buf + L.offsets;
   float* temp = reinterpret_cast<float*>(buf + L.temperature);
   int32_t* tk = buf + L.top_k;
+  int32_t* lpn = buf + L.lp_n;
+  int32_t nlp = 0;
   float* tp = reinterpret_cast<float*>(buf + L.top_p);
   int32_t ntrunc = 0;
   int64_t* seeds = reinterpret_cast<int64_t*>(buf + L.seeds);
@@ -456,6 +479,8 @@ int32_t Scheduler::schedule(int32_t* buf) {
       tp[nsamp] = s->top_p;
       if (s->temperature > 0.f && (s->top_k > 0 || s->top_p < 1.f) && forced < 0) ++ntrunc;
       seeds[nsamp] = s->seed;
+      lpn[nsamp] = s->logprobs;
+      if (s->logprobs >= 0) ++nlp;
       ++nsamp;
     }
     // attention work items (mirrors pilottai_amd/ops/attn_meta.py)
@@ -530,6 +555,7 @@ int32_t Scheduler::schedule(int32_t* buf) {
     tk[r] = 0;
     tp[r] = 1.f;
     seeds[r] = 0;
+    lpn[r] = -1;
   }
   for (int32_t r = ns; r < L.max_seqs; ++r) {
     qs[r] = T;
@@ -544,6 +570,8 @@ int32_t Scheduler::schedule(int32_t* buf) {
   counts[5] = pslot;
   counts[6] = ntrunc;  // rows that need the top-k / top-p threshold pass
   counts[7] = nembed;  // tokens whose hidden states are pooled (embedding requests)
+  counts[8] = nlp;     // rows that need the log-probability pass
+  counts[9] = counts[10] = counts[11] = 0;
   if (nit > L.max_items)  // by construction (psz guard above, max_items sizing) this cannot happen
     throw std::logic_error("scheduler: attention item list overflows max_items");
   buf[L.n_items] = nit;
@@ -596,12 +624,15 @@ SeqOutput Scheduler::finish(Sequence* s, int32_t reason, double now) {
   o.t_first_token = s->t_first_token;
   o.t_finish = now;
   o.embed_slot = s->embed_slot;  // FINISH_EMBED: read it; otherwise: clear it before reuse
+  o.logprobs = s->logprobs;
+  o.lp_records = std::move(s->lp_records);
+  s->lp_records.clear();
   free_seq(s);
   s->running = false;
   return o;
 }
 
-std::vector<SeqOutput> Scheduler::commit(const int32_t* sampled, int32_t n) {
+std::vector<SeqOutput> Scheduler::commit(const int32_t* sampled, int32_t n, const LogprobRecord* lp) {
   std::vector<SeqOutput> outs;
   if (plans_.empty()) return outs;
   Plan plan = std::move(plans_.front());
@@ -632,6 +663,15 @@ std::vector<SeqOutput> Scheduler::commit(const int32_t* sampled, int32_t n) {
     s->tokens.push_back(tok);
     ++s->num_generated;
     ++s->num_sampled;
+    if (s->logprobs >= 0) {
+      if (lp) {
+        s->lp_records.push_back(lp[idx - 1]);
+      } else {  // the step computed no records: keep the alignment with the tokens
+        LogprobRecord r = forced_record(tok, 0);
+        r.lp = NAN;
+        s->lp_records.push_back(r);
+      }
+    }
     int32_t fin = NOT_FINISHED;
     if (s->grammar) {
       s->grammar->advance(tok);
@@ -649,6 +689,9 @@ std::vector<SeqOutput> Scheduler::commit(const int32_t* sampled, int32_t n) {
       const int32_t k = s->grammar->take_forced_run(s->tokens, room);
       s->num_generated += k;
       s->num_forced += k;
+      if (s->logprobs >= 0)
+        for (int32_t j = k; j > 0; --j)
+          s->lp_records.push_back(forced_record(s->tokens[s->tokens.size() - j], s->logprobs));
       if (s->grammar->done()) fin = FINISH_STOP;
       else if (s->num_generated >= s->max_tokens) fin = FINISH_LENGTH;
     }

@@ -84,6 +84,7 @@ struct StepLayout {
   int32_t max_tokens, max_seqs, max_blocks, max_items;
   int32_t input_ids, positions, slots, q_start, q_len, ctx_len, logit_rows, mask_class, forced,
       offsets, temperature, top_k, top_p, seeds, items, n_items, part_size, counts, block_table, total;
+  int32_t lp_n;        // [max_seqs]: alternatives asked per sampling row (log-probabilities), -1 = none
   int32_t embed_rows;  // [max_tokens]: pooling row of each token (embedding requests), max_seqs = none
 };
 
@@ -91,6 +92,17 @@ enum FinishReason : int32_t {
   NOT_FINISHED = -1, FINISH_STOP = 0, FINISH_LENGTH = 1, FINISH_ABORT = 2,
   FINISH_EMBED = 3  // embedding request: prompt fully prefilled, pooled hidden state ready
 };
+
+// Log-probability record of one generated token, as the device writes it per sampling row
+// (csrc/ops/sampling.hip logprob_merge_kernel): the chosen token's logprob, then up to
+// LOGPROB_TOP (token id, logprob) alternatives by descending logit (id -1 / -inf past the end).
+constexpr int32_t LOGPROB_TOP = 20;
+struct LogprobRecord {
+  float lp;
+  int32_t ids[LOGPROB_TOP];
+  float lps[LOGPROB_TOP];
+};
+static_assert(sizeof(LogprobRecord) == 4 * (1 + 2 * LOGPROB_TOP), "LogprobRecord is 41 packed 32-bit words");
 
 struct SeqOutput {
   int64_t id;
@@ -103,6 +115,8 @@ struct SeqOutput {
   double t_first_token;
   double t_finish;
   int32_t embed_slot = -1;  // pooling row of an embedding request (FINISH_EMBED: holds the sums)
+  int32_t logprobs = -1;    // alternatives the request asked for (-1: it did not ask)
+  std::vector<LogprobRecord> lp_records;  // logprobs >= 0: one per entry of `tokens`
 };
 
 struct Sequence {
@@ -125,6 +139,8 @@ struct Sequence {
   float top_p = 1.0f;   // 1 = no nucleus truncation
   int32_t max_tokens = 256;
   int64_t seed = 0;
+  int32_t logprobs = -1;  // >= 0: log-probability records are kept, with this many alternatives
+  std::vector<LogprobRecord> lp_records;  // one per generated token (tokens[prompt_len:])
   bool ignore_eos = false;
   std::vector<int32_t> stop_ids;
   int64_t arrival = 0;
@@ -158,7 +174,7 @@ class Scheduler {
   void add_request(int64_t id, std::vector<int32_t> prompt, float temperature, int32_t max_tokens,
                    int64_t seed, bool ignore_eos, std::vector<int32_t> stop_ids,
                    std::unique_ptr<Grammar> grammar, int32_t top_k = 0, float top_p = 1.0f,
-                   bool embed = false, bool embed_last = false);
+                   bool embed = false, bool embed_last = false, int32_t logprobs = -1);
   bool abort(int64_t id);
   // Fill `buf` (layout()) for the next step. Returns the number of tokens in the
   // step (0 = nothing to run).
@@ -175,7 +191,9 @@ class Scheduler {
   // recomputed) — only the sampled token's own KV is kept, and it is always right.
   int32_t schedule(int32_t* buf);
   // Consume the sampled tokens of the oldest uncommitted step (one per sampling row).
-  std::vector<SeqOutput> commit(const int32_t* sampled, int32_t n);
+  // `lp`: the step's log-probability records, one per sampling row (nullptr: the step computed
+  // none); rows of requests that did not ask hold nothing meaningful and are not read.
+  std::vector<SeqOutput> commit(const int32_t* sampled, int32_t n, const LogprobRecord* lp = nullptr);
   int32_t inflight_steps() const { return (int32_t)plans_.size(); }
   int64_t spec_rows() const { return stat_spec_rows_; }
   int64_t spec_voided() const { return stat_spec_voided_; }

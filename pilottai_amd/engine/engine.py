@@ -37,7 +37,7 @@ from collections import deque
 import threading
 import time
 from dataclasses import dataclass, field
-from typing import Any, Callable, Dict, List, Optional, Sequence, Union
+from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -166,6 +166,11 @@ class GenerationOutput:
     t_finish: float
     _tok: Optional[Tokenizer] = field(default=None, repr=False)
     embedding: Optional[np.ndarray] = field(default=None, repr=False)  # embedding requests: mean final hidden
+    # submit(logprobs=n >= 0): per entry of token_ids (logprob of the token, [(token id, logprob)]
+    # of the <= n most likely tokens the grammar allowed there, most likely first); natural log
+    # of softmax(logits) over the allowed tokens at temperature 1; grammar-forced tokens have 0.0
+    logprobs: Optional[List[Tuple[float, List[Tuple[int, float]]]]] = field(default=None, repr=False)
+    cumulative_logprob: Optional[float] = None  # sum of the tokens' logprobs (None: not asked)
 
     @property
     def text(self) -> str:
@@ -199,6 +204,7 @@ class _Request:
     top_p: float = 1.0
     embed: bool = False
     embed_last: bool = False  # last-token pooling (prefix-cache reuse allowed)
+    logprobs: int = -1        # -1 off, 0 the chosen token only, 1..20 with that many alternatives
 
 
 class LLMEngine:
@@ -355,8 +361,21 @@ class LLMEngine:
         self._part_o = ops.empty_handoff(max_items * kv_local * 16 * 128, torch.float32, self.device)
         self._part_ml = ops.empty_handoff(max_items * kv_local * 16 * 2, torch.float32, self.device)
         self._sample_ws = ops.sample_workspace(S, self.model.v_local, self.device) if self.on_gpu else None
-        # one graph per (token bucket, top-k/top-p pass); truncating variants are
-        # captured on first use, so steps without truncation pay nothing for it
+        # log-probabilities (submit(logprobs=n)): one 41-word record per sampling row (logprob,
+        # 20 ids, 20 logprobs: the scheduler's LogprobRecord), written by ops.token_logprobs
+        # behind the sampler in the step graph's logprob variant and copied to the host with the
+        # sampled tokens. TP > 1 is refused at submit() (vocab-parallel LM head).
+        W = self._rt.Scheduler.LOGPROB_RECORD_WORDS
+        assert W == 1 + 2 * ops.LOGPROB_TOP
+        self._lp_rec = torch.zeros(S, W, dtype=torch.int32, device=self.device)
+        recf = self._lp_rec.view(torch.float32)
+        self._lp_out = (recf[:, 0], self._lp_rec[:, 1:1 + ops.LOGPROB_TOP], recf[:, 1 + ops.LOGPROB_TOP:])
+        self._lp_hosts = [torch.zeros(S, W, dtype=torch.int32, pin_memory=pin) for _ in range(nbuf)]
+        self._lp_ws = ops.token_logprobs_workspace(S, self.model.v_local, self.device) \
+            if (self.on_gpu and self.tp.size == 1) else None
+        # one graph per (token bucket, top-k/top-p pass, embedding pooling); truncating variants
+        # are captured on first use, so steps without truncation pay nothing for it. The variant
+        # with the log-probability pass has the 4-tuple key (bucket, trunc, embed, True).
         self._graphs: Dict[tuple, "torch.cuda.CUDAGraph"] = {}
         self._tau = torch.empty(S, dtype=torch.float32, device=self.device)
         self._graph_pool = None
@@ -444,6 +463,7 @@ class LLMEngine:
         self._forced = sl("forced", ms)
         self._offsets = sl("offsets", ms)
         self._seeds = sl("seeds", 2 * ms).view(torch.int64)
+        self._lp_n = sl("lp_n", ms)
 
     def _sync_masks(self) -> bool:
         reg = self.grammar.reg
@@ -464,7 +484,8 @@ class LLMEngine:
                         m.block_table, m.items[:n_it], m.n_items, m.att_counters, m.logit_rows, num_seqs=ns,
                         part_size=m.part_size)
 
-    def _forward_and_sample(self, bucket: int, s_b: int, ns: int, trunc: bool = False, embed: bool = False):
+    def _forward_and_sample(self, bucket: int, s_b: int, ns: int, trunc: bool = False, embed: bool = False,
+                            lp: bool = False):
         meta = self._meta_for(bucket, s_b, ns)
         if self._async:  # pending tokens of rows that sampled in the previous step
             ops.patch_pending_ids(meta.input_ids[:bucket], self._sampled_dev)
@@ -499,23 +520,34 @@ class LLMEngine:
             toks = self.tp.all_gather(self._sampled_dev[:s4])[:, :s_b]     # [tp, s_b]
             best = keys.argmax(0, keepdim=True)
             self._sampled_dev[:s_b].copy_(toks.gather(0, best).squeeze(0))
+        if lp:
+            o_lp, o_ids, o_lps = self._lp_out
+            ops.token_logprobs(logits, self._sampled_dev[:s_b], self._lp_n[:s_b], self._forced[:s_b],
+                               self._mask_cls[:s_b], self._class_masks,
+                               out=(o_lp[:s_b], o_ids[:s_b], o_lps[:s_b]), workspace=self._lp_ws)
 
-    def _run(self, bucket: int, ns: int, trunc: bool, n_copy: int, embed: bool = False):
-        """Replay the (bucket, trunc, embed) graph — capturing it first if needed — or run eagerly."""
+    @staticmethod
+    def _graph_key(bucket: int, trunc: bool, embed: bool, lp: bool = False) -> tuple:
+        return (bucket, trunc, embed, True) if lp else (bucket, trunc, embed)
+
+    def _run(self, bucket: int, ns: int, trunc: bool, n_copy: int, embed: bool = False, lp: bool = False):
+        """Replay the (bucket, trunc, embed[, logprobs]) graph — capturing it first if needed — or
+        run eagerly."""
         if not self.use_graphs:
-            self._forward_and_sample(bucket, self._seq_bucket(bucket), ns, trunc, embed)
+            self._forward_and_sample(bucket, self._seq_bucket(bucket), ns, trunc, embed, lp)
             return
-        g = self._graphs.get((bucket, trunc, embed))
+        key = self._graph_key(bucket, trunc, embed, lp)
+        g = self._graphs.get(key)
         if g is None:
             saved = self._dev_meta[:n_copy].clone()
             pool = self._embed_pool.clone()
             samp = self._sampled_dev.clone()  # the previous step's tokens (pipelined mode)
-            self.capture_graphs([bucket], trunc=trunc, embed=embed)  # clobbers the device metadata
+            self.capture_graphs([bucket], trunc=trunc, embed=embed, lp=lp)  # clobbers the device metadata
             self.stats["graph_captures"] += 1  # a first-use capture inside serving (tens of ms)
             self._dev_meta[:n_copy].copy_(saved)
             self._embed_pool.copy_(pool)
             self._sampled_dev.copy_(samp)
-            g = self._graphs[(bucket, trunc, embed)]
+            g = self._graphs[key]
         g.replay()
         self.stats["graph_replays"] += 1
 
@@ -537,9 +569,10 @@ class LLMEngine:
             raise RuntimeError("capture_embed_graphs() runs before start()")
         self.capture_graphs(embed=True)
 
-    def capture_graphs(self, buckets: Optional[Sequence[int]] = None, trunc: bool = False, embed: bool = False):
-        """Capture one hipGraph per token bucket (shared memory pool); the top-k/top-p and
-        embedding-pooling variants are captured on first use."""
+    def capture_graphs(self, buckets: Optional[Sequence[int]] = None, trunc: bool = False, embed: bool = False,
+                       lp: bool = False):
+        """Capture one hipGraph per token bucket (shared memory pool); the top-k/top-p,
+        embedding-pooling and log-probability variants are captured on first use."""
         if not self.use_graphs:
             return
         self._dummy_meta()
@@ -547,21 +580,22 @@ class LLMEngine:
             self._graph_pool = torch.cuda.graph_pool_handle()
         t0 = time.time()
         for b in sorted(buckets or self.buckets, reverse=True):
-            if (b, trunc, embed) in self._graphs:
+            key = self._graph_key(b, trunc, embed, lp)
+            if key in self._graphs:
                 continue
             s_b = self._seq_bucket(b)
             st = torch.cuda.Stream(device=self.device)
             st.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(st):
                 for _ in range(2):
-                    self._forward_and_sample(b, s_b, 0, trunc, embed)
+                    self._forward_and_sample(b, s_b, 0, trunc, embed, lp)
             torch.cuda.current_stream().wait_stream(st)
             g = torch.cuda.CUDAGraph(keep_graph=True) if self.cfg.keep_graphs else torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, pool=self._graph_pool):
-                self._forward_and_sample(b, s_b, 0, trunc, embed)
+                self._forward_and_sample(b, s_b, 0, trunc, embed, lp)
             if self.cfg.keep_graphs:
                 g.instantiate()
-            self._graphs[(b, trunc, embed)] = g
+            self._graphs[key] = g
         if embed:
             self._embed_pool.zero_()  # the capture's dummy steps pooled into row max_seqs only
         torch.cuda.synchronize()
@@ -578,7 +612,7 @@ class LLMEngine:
                temperature: float = 0.7, max_tokens: int = 256, seed: Optional[int] = None,
                ignore_eos: bool = False, stop_ids: Sequence[int] = (), grammar: Optional[list] = None,
                request_id: Optional[int] = None, top_k: int = 0, top_p: float = 1.0,
-               embed: Union[bool, str] = False) -> int:
+               embed: Union[bool, str] = False, logprobs: int = -1) -> int:
         """Thread-safe; `callback` runs on the engine thread when the request finishes.
 
         top_k > 0 / top_p < 1 truncate the (grammar-masked) distribution before
@@ -587,15 +621,28 @@ class LLMEngine:
         reuse), nothing is sampled, and the output carries the mean final-norm hidden state.
         embed="last": the final-norm hidden state of the prompt's last token; since a token's
         state depends only on its prefix, such requests reuse cached prefix blocks (shared
-        task text across an agent's lookups is computed once)."""
+        task text across an agent's lookups is computed once).
+
+        logprobs = n: -1 off; 0..20: the output carries, per generated token, its log-probability
+        and the n most likely alternatives (GenerationOutput.logprobs) under softmax(logits) over
+        the tokens the grammar allowed, at temperature 1 -- whatever temperature / top_k / top_p
+        the token was sampled with. Not for embedding requests, not on a TP > 1 engine."""
         if self._err is not None:
             raise RuntimeError(f"engine failed: {self._err!r}")
+        logprobs = -1 if logprobs is None else int(logprobs)
+        if not -1 <= logprobs <= ops.LOGPROB_TOP:
+            raise ValueError(f"logprobs must be -1 (off) or 0..{ops.LOGPROB_TOP}, not {logprobs}")
+        if logprobs >= 0 and embed:
+            raise ValueError("logprobs are not available on embedding requests")
+        if logprobs >= 0 and self.tp.size > 1:
+            raise ValueError("logprobs are not supported on a tensor-parallel (TP > 1) engine")
         rid = request_id if request_id is not None else self.new_request_id()
         if seed is None:
             seed = (self.cfg.seed * 0x9E3779B1 + rid * 0x85EBCA77) & 0x7FFFFFFFFFFFFFFF
         req = _Request(rid, list(prompt_ids), float(temperature), int(max_tokens), int(seed),
                        bool(ignore_eos), list(stop_ids), grammar, callback, self._rt.now(),
-                       int(top_k or 0), float(1.0 if top_p is None else top_p), bool(embed), embed == "last")
+                       int(top_k or 0), float(1.0 if top_p is None else top_p), bool(embed), embed == "last",
+                       logprobs)
         self._inbox.put(req)
         self._wake.set()
         return rid
@@ -827,7 +874,7 @@ class LLMEngine:
             self._reqs[req.rid] = req
             self.sched.add_request(req.rid, req.prompt_ids, req.temperature, req.max_tokens, req.seed,
                                    req.ignore_eos, req.stop_ids, req.grammar, req.top_k, req.top_p, req.embed,
-                                   req.embed_last)
+                                   req.embed_last, req.logprobs)
             self.stats["requests"] += 1
         while True:
             try:
@@ -839,7 +886,7 @@ class LLMEngine:
             self._deliver(o)
 
     def _deliver(self, o):
-        rid, toks, reason, plen, cached, nsamp, nforced, t_first, t_fin, eslot = o
+        rid, toks, reason, plen, cached, nsamp, nforced, t_first, t_fin, eslot, lps = o
         emb = None
         if eslot >= 0 and eslot in self._embed_ready:  # read back when its step committed
             emb = self._embed_ready.pop(eslot)
@@ -856,7 +903,8 @@ class LLMEngine:
         if req is None:
             return
         out = GenerationOutput(rid, list(toks), _REASONS.get(reason, "stop"), plen, cached, len(toks),
-                               nsamp, nforced, req.t_arrival, t_first, t_fin, self.tok, emb)
+                               nsamp, nforced, req.t_arrival, t_first, t_fin, self.tok, emb,
+                               lps, None if lps is None else float(sum(e[0] for e in lps)))
         # per-request timings: TTFT = arrival -> first token, TPOT = later tokens' mean gap
         if t_first > 0:
             n_out = max(1, len(toks))
@@ -884,8 +932,8 @@ class LLMEngine:
             if self.sched.num_running == 0 and self.sched.num_waiting > 0:
                 raise RuntimeError("KV cache too small for the head request")
             return False
-        c = self._host_np[L["counts"]:L["counts"] + 8]
-        ns, nsamp, trunc, embed = int(c[1]), int(c[2]), int(c[6]) > 0, int(c[7]) > 0
+        c = self._host_np[L["counts"]:L["counts"] + 9]
+        ns, nsamp, trunc, embed, lp = int(c[1]), int(c[2]), int(c[6]) > 0, int(c[7]) > 0, int(c[8]) > 0
         bucket = next(b for b in self.buckets if b >= T)
         s_b = self._seq_bucket(bucket)
         masks_changed = self._sync_masks()
@@ -901,11 +949,13 @@ class LLMEngine:
                 self.tp.broadcast(self._class_masks)
             self.tp.broadcast(self._dev_meta[:n_copy])
         with torch.inference_mode(), trace_range("engine.forward"):
-            self._run(bucket, ns, trunc, n_copy, embed)
+            self._run(bucket, ns, trunc, n_copy, embed, lp)
         if self._step_listeners:
             self._notify_launch(T)
         if nsamp:
             self._sampled_host[:nsamp].copy_(self._sampled_dev[:nsamp], non_blocking=self.on_gpu)
+        if lp:
+            self._lp_hosts[0][:nsamp].copy_(self._lp_rec[:nsamp], non_blocking=self.on_gpu)
         self._health_fetch()
         t_launch = time.perf_counter()
         # the previous step's finished requests are handed to their callers while this step
@@ -917,7 +967,8 @@ class LLMEngine:
         self._health_check()
         t_sync = time.perf_counter()
         with trace_range("engine.commit"):
-            outs = self.sched.commit(self._sampled_host.data_ptr(), nsamp)
+            outs = self.sched.commit(self._sampled_host.data_ptr(), nsamp,
+                                     self._lp_hosts[0].data_ptr() if lp else 0)
         if embed:
             self._read_embeddings(outs)
         st = self.stats
@@ -971,8 +1022,8 @@ class LLMEngine:
             if not self._inflight and self.sched.num_running == 0 and self.sched.num_waiting > 0:
                 raise RuntimeError("KV cache too small for the head request")
             return False
-        c = hm.numpy()[L["counts"]:L["counts"] + 8]
-        ns, nsamp, trunc, embed = int(c[1]), int(c[2]), int(c[6]) > 0, int(c[7]) > 0
+        c = hm.numpy()[L["counts"]:L["counts"] + 9]
+        ns, nsamp, trunc, embed, lp = int(c[1]), int(c[2]), int(c[6]) > 0, int(c[7]) > 0, int(c[8]) > 0
         bucket = next(b for b in self.buckets if b >= T)
         self._sync_masks()
         n_copy = L["embed_rows"] + bucket if embed else L["block_table"] + ns * L["max_blocks"]
@@ -981,11 +1032,13 @@ class LLMEngine:
             self._embed_pool[torch.tensor(resets, dtype=torch.long, device=self.device)] = 0.0
         self._dev_meta[:n_copy].copy_(hm[:n_copy], non_blocking=self.on_gpu)
         with torch.inference_mode(), trace_range("engine.forward"):
-            self._run(bucket, ns, trunc, n_copy, embed)
+            self._run(bucket, ns, trunc, n_copy, embed, lp)
         if self._step_listeners:
             self._notify_launch(T)
         if nsamp:
             self._sampled_hosts[slot][:nsamp].copy_(self._sampled_dev[:nsamp], non_blocking=self.on_gpu)
+        if lp:
+            self._lp_hosts[slot][:nsamp].copy_(self._lp_rec[:nsamp], non_blocking=self.on_gpu)
         if embed:
             self._embed_hosts[slot].copy_(self._embed_pool, non_blocking=self.on_gpu)
         self._health_fetch()
@@ -994,7 +1047,7 @@ class LLMEngine:
             ev = torch.cuda.Event()
             ev.record()
         t_launch = time.perf_counter()
-        self._inflight.append((slot, T, bucket, nsamp, embed, ev, t0))
+        self._inflight.append((slot, T, bucket, nsamp, embed, ev, t0, lp))
         self._slot = (slot + 1) % len(self._host_metas)
         st = self.stats
         st["host_sched_s"] += t_sched - t0
@@ -1004,14 +1057,15 @@ class LLMEngine:
         return True
 
     def _complete(self, rec):
-        slot, T, bucket, nsamp, embed, ev, t0 = rec
+        slot, T, bucket, nsamp, embed, ev, t0, lp = rec
         t_w = time.perf_counter()
         if ev is not None:
             ev.synchronize()
         self._health_check()
         t_sync = time.perf_counter()
         with trace_range("engine.commit"):
-            outs = self.sched.commit(self._sampled_hosts[slot].data_ptr(), nsamp)
+            outs = self.sched.commit(self._sampled_hosts[slot].data_ptr(), nsamp,
+                                     self._lp_hosts[slot].data_ptr() if lp else 0)
         if embed:
             self._read_embeddings(outs, self._embed_hosts[slot])
         st = self.stats

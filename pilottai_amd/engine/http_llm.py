@@ -11,7 +11,8 @@ Structured replies: agents pass `response_format={"schema": <rules.yaml name>,
 "fixed": {...}}`. Against a pilottai server that is forwarded as the
 `pilottai_schema` extension (grammar-constrained on the server). Against another
 OpenAI-compatible server, pass `schema_mode="json_object"` to send
-`{"type": "json_object"}` instead.
+`{"type": "json_object"}` instead. `response_format["logprobs"] = n` (0..20) is sent as
+`logprobs: true, top_logprobs: n`; the reply's `logprobs.content` comes back as `r["logprobs"]`.
 
     LLMConfig(provider="openai", base_url="http://10.0.0.5:8000/v1", api_key=...)
 """
@@ -24,6 +25,7 @@ from .local_llm import BaseLLM, _cfg_get
 
 class OpenAICompatLLM(BaseLLM):
     provider = "openai"
+    supports_logprobs = True
 
     def __init__(self, config: Any = None, base_url: Optional[str] = None, timeout_s: float = 600.0,
                  schema_mode: str = "pilottai"):
@@ -57,6 +59,9 @@ class OpenAICompatLLM(BaseLLM):
                                 "max_tokens": int(rf.get("max_tokens", self.max_tokens))}
         if rf.get("seed") is not None:
             body["seed"] = rf["seed"]
+        if rf.get("logprobs") is not None and int(rf["logprobs"]) >= 0:
+            body["logprobs"] = True
+            body["top_logprobs"] = int(rf["logprobs"])
         if tools:
             body["tools"] = self._format_tools(tools)
         elif rf.get("schema") is not None:
@@ -79,6 +84,7 @@ class OpenAICompatLLM(BaseLLM):
         pt, ct = int(usage.get("prompt_tokens", 0)), int(usage.get("completion_tokens", 0))
         return {"content": msg.get("content") or "", "role": msg.get("role", "assistant"),
                 "tool_calls": msg.get("tool_calls"), "model": data.get("model", self.model_name),
+                "logprobs": (ch.get("logprobs") or {}).get("content"),
                 "usage": {"prompt_tokens": pt, "completion_tokens": ct, "total_tokens": pt + ct}}
 
     async def list_models(self) -> List[str]:

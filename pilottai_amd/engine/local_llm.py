@@ -55,6 +55,24 @@ def encode_chat(tok: Tokenizer, messages: Sequence[Dict[str, str]]) -> List[int]
     return ids
 
 
+def logprob_entries(tok: Tokenizer, token_ids: Sequence[int], logprobs) -> List[Dict[str, Any]]:
+    """GenerationOutput.logprobs in the OpenAI `logprobs.content` shape (plus token ids): one
+    {"token", "token_id", "logprob", "bytes", "top_logprobs": [{"token", "token_id", "logprob",
+    "bytes"}]} per generated token, every token decoded on its own."""
+
+    def one(tid: int, lp: float) -> Dict[str, Any]:
+        raw = tok.decode_bytes([int(tid)])
+        return {"token": raw.decode("utf-8", errors="replace"), "token_id": int(tid), "logprob": float(lp),
+                "bytes": list(raw)}
+
+    out = []
+    for tid, (lp, top) in zip(token_ids, logprobs):
+        e = one(tid, lp)
+        e["top_logprobs"] = [one(i, v) for i, v in top]
+        out.append(e)
+    return out
+
+
 def _cfg_get(config: Any, key: str, default=None):
     if config is None:
         return default
@@ -91,6 +109,7 @@ class BaseLLM:
     """Shared protocol surface (rate limit, retries, response shaping)."""
 
     provider = "base"
+    supports_logprobs = False  # response_format["logprobs"] is honoured and r["logprobs"] returned
 
     def __init__(self, config: Any = None):
         self.config = config
@@ -169,6 +188,7 @@ class LocalLLM(BaseLLM):
     """Reference LLMHandler contract backed by the local MI355X engine."""
 
     provider = "local"
+    supports_logprobs = True
     prefix_cache_layout = True  # agents put the shared task text first (core/agent.py)
 
     def __init__(self, config: Any = None, engine=None):
@@ -211,7 +231,8 @@ class LocalLLM(BaseLLM):
         rid = self.engine.submit(ids, done, temperature=temp, max_tokens=int(rf.get("max_tokens", self.max_tokens)),
                                  grammar=grammar,
                                  seed=rf.get("seed"), top_k=int(rf.get("top_k", self.top_k)),
-                                 top_p=float(rf.get("top_p", self.top_p)))
+                                 top_p=float(rf.get("top_p", self.top_p)),
+                                 logprobs=-1 if rf.get("logprobs") is None else int(rf["logprobs"]))
         try:
             out = await fut
         except asyncio.CancelledError:
@@ -233,6 +254,9 @@ class LocalLLM(BaseLLM):
             "content": text,
             "role": "assistant",
             "tool_calls": tool_calls,
+            # response_format["logprobs"] = n (0..20): per generated token, its log-probability and
+            # the n most likely alternatives among the tokens the grammar allowed (None: not asked)
+            "logprobs": None if out.logprobs is None else logprob_entries(self.tok, out.token_ids, out.logprobs),
             "model": self.engine.model_cfg.name,
             "usage": {"prompt_tokens": out.prompt_tokens, "completion_tokens": out.completion_tokens,
                       "total_tokens": out.prompt_tokens + out.completion_tokens},

@@ -190,6 +190,10 @@ class Tokenizer:
     def decode(self, ids: Sequence[int]) -> str:
         return self._native.decode(list(ids)).decode("utf-8", errors="replace")
 
+    def decode_bytes(self, ids: Sequence[int]) -> bytes:
+        """The raw bytes of `ids` (a single token may end inside a UTF-8 sequence)."""
+        return self._native.decode(list(ids))
+
     def token_id(self, piece: str) -> int:
         return self._native.lookup(piece.encode("utf-8"))
 

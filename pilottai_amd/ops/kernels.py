@@ -202,6 +202,45 @@ def sample(logits, temperature, mask_class, class_masks, seeds, offsets, forced=
     return toks
 
 
+LOGPROB_TOP = 20             # alternatives per token the log-probability pass can return
+TOKEN_LOGPROBS_LAUNCHES = 2  # kernels token_logprobs() launches on the GPU (chunk pass + row merge)
+
+
+def token_logprobs_workspace(rows: int, V: int, device) -> torch.Tensor:
+    n = require_native().logprob_workspace_floats(rows, V)
+    return torch.empty(n, dtype=torch.float32, device=device)
+
+
+def token_logprobs(logits, tokens, lp_n, forced, mask_class, class_masks, out=None,
+                   workspace: Optional[torch.Tensor] = None):
+    """Log-probabilities of the sampled `tokens` and of the lp_n[row] most likely alternatives
+    (csrc/ops/sampling.hip): natural log of softmax(logits) over the tokens the row's mask class
+    allows, at temperature 1. Returns / fills `out` = (logprob fp32 [rows], top_ids int32
+    [rows, 20], top_lp fp32 [rows, 20]); the lists are sorted by logit descending, equal logits
+    by smaller id, and end with id -1 / -inf. Rows with lp_n < 0 are left untouched; rows with
+    forced >= 0 get (0.0, [(forced, 0.0)]); a row whose mask allows nothing gets -inf and an
+    empty list. The outputs may be strided columns of one record buffer."""
+    rows = logits.shape[0]
+    if out is None:
+        out = (torch.empty(rows, dtype=torch.float32, device=logits.device),
+               torch.empty(rows, LOGPROB_TOP, dtype=torch.int32, device=logits.device),
+               torch.empty(rows, LOGPROB_TOP, dtype=torch.float32, device=logits.device))
+    lp, ids, lps = out
+    if _on_gpu(logits):
+        C = require_native()
+        if workspace is None:
+            workspace = token_logprobs_workspace(rows, logits.shape[1], logits.device)
+        C.token_logprobs(lp, ids, lps, workspace, logits, tokens, lp_n, forced, mask_class, class_masks)
+        return out
+    r_lp, r_ids, r_lps = ref.token_logprobs(logits, tokens, lp_n, forced, mask_class, class_masks)
+    asked = (lp_n[:rows] >= 0).cpu()
+    if bool(asked.any()):
+        lp[:rows][asked] = r_lp[asked]
+        ids[:rows][asked] = r_ids[asked]
+        lps[:rows][asked] = r_lps[asked]
+    return out
+
+
 COSINE_MAX_Q = 64  # queries per index pass (LDS-resident query tiles)
 
 

@@ -223,6 +223,56 @@ def sample(logits: torch.Tensor, temperature, mask_class, class_masks, seeds, of
     return (toks, keys_out) if return_keys else toks
 
 
+def token_logprobs(logits: torch.Tensor, tokens, lp_n, forced, mask_class, class_masks, top: int = 20):
+    """Per-token log-probabilities (fp64 math, sort based): log softmax(logits) over the tokens
+    the row's mask class allows, at temperature 1.
+
+    Returns (logprob fp32 [rows], top_ids int32 [rows, top], top_lp fp32 [rows, top]). A row
+    lists its min(lp_n, top) most likely allowed tokens by descending logit, equal logits by
+    smaller id, then id -1 / -inf. Rows with lp_n < 0 keep NaN / -1 / NaN (skipped); rows with
+    forced >= 0 give (0.0, [(forced, 0.0)]); a row whose mask allows nothing gives -inf and an
+    empty list. A chosen token the mask does not allow has logprob -inf; logits of -inf are
+    never listed."""
+    rows, V = logits.shape
+    out_lp = torch.full((rows,), float("nan"), dtype=torch.float32)
+    out_ids = torch.full((rows, top), -1, dtype=torch.int32)
+    out_lps = torch.full((rows, top), float("nan"), dtype=torch.float32)
+    lg = logits.float().cpu().numpy().astype(np.float64)
+    cm = class_masks.cpu().numpy().view(np.uint32) if class_masks is not None else None
+    idx = np.arange(V)
+    for r in range(rows):
+        n = int(lp_n[r])
+        if n < 0:
+            continue
+        n = min(n, top)
+        out_lps[r] = float("-inf")
+        f = int(forced[r]) if forced is not None else -1
+        if f >= 0:
+            out_lp[r] = 0.0
+            if n > 0:
+                out_ids[r, 0] = f
+                out_lps[r, 0] = 0.0
+            continue
+        mc = int(mask_class[r])
+        valid = np.ones(V, dtype=bool)
+        if mc >= 0 and cm is not None:
+            valid = ((cm[mc][idx >> 5] >> (idx & 31).astype(np.uint32)) & 1).astype(bool)
+        x = np.where(valid, lg[r], -np.inf)
+        mx = x.max()
+        if not mx > -np.inf:
+            out_lp[r] = float("-inf")
+            continue
+        lse = mx + np.log(np.exp(x - mx).sum())
+        t = int(tokens[r])
+        out_lp[r] = float(x[t] - lse) if 0 <= t < V else float("-inf")
+        if n > 0:
+            order = np.argsort(-x, kind="stable")[:n]  # stable: equal logits keep ascending ids
+            order = order[x[order] > -np.inf]
+            out_ids[r, :order.size] = torch.from_numpy(order.astype(np.int32))
+            out_lps[r, :order.size] = torch.from_numpy((x[order] - lse).astype(np.float32))
+    return out_lp, out_ids, out_lps
+
+
 # ---------------------------------------------------------------------------
 # semantic index
 # ---------------------------------------------------------------------------

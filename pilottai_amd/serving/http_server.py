@@ -21,6 +21,11 @@ speak:
 `tools` (OpenAI function tools) produce a constrained `{"name", "arguments"}` call,
 returned as `tool_calls`.
 
+`logprobs: true` (with `top_logprobs: 0..20`) returns `choices[0].logprobs.content`: per
+generated token its log-probability and the most likely alternatives, under softmax(logits)
+over the tokens the reply's grammar allowed at that position, at temperature 1 (a
+grammar-forced token has 0.0). Each entry also carries `token_id`; -inf is sent as -9999.0.
+
 Every request becomes one `LocalLLM` call, i.e. one sequence in the engine's continuous
 batch. Concurrent HTTP clients share the engine's steps exactly like in-process agents.
 
@@ -108,6 +113,31 @@ def _response_format(body: Dict[str, Any]) -> Optional[Dict[str, Any]]:
     return out
 
 
+def _logprobs(body: Dict[str, Any]) -> int:
+    """The number of alternatives asked for (-1: no logprobs), from `logprobs` / `top_logprobs`."""
+    want, top = body.get("logprobs"), body.get("top_logprobs")
+    if want is not None and not isinstance(want, bool):
+        raise ValueError("logprobs must be a boolean")
+    if top is None:
+        return 0 if want else -1
+    if isinstance(top, bool) or not isinstance(top, int) or not 0 <= top <= 20:
+        raise ValueError("top_logprobs must be an integer between 0 and 20")
+    if not want:
+        raise ValueError("top_logprobs requires logprobs: true")
+    return top
+
+
+def _wire_logprobs(entries: List[Dict[str, Any]]) -> Dict[str, Any]:
+    def lp(v: float) -> float:
+        return -9999.0 if v == float("-inf") or v != v else float(v)
+
+    def one(e: Dict[str, Any]) -> Dict[str, Any]:
+        return {"token": e["token"], "token_id": e.get("token_id"), "logprob": lp(e["logprob"]),
+                "bytes": e.get("bytes")}
+
+    return {"content": [dict(one(e), top_logprobs=[one(t) for t in e.get("top_logprobs", [])]) for e in entries]}
+
+
 def _tools(body: Dict[str, Any]) -> Optional[List[Dict[str, Any]]]:
     tools = body.get("tools")
     if not tools:
@@ -155,8 +185,13 @@ def create_app(llm, model_name: Optional[str] = None, engine=None) -> FastAPI:
         try:
             rf = _response_format(body)
             tools = _tools(body)
+            n_lp = _logprobs(body)
         except (KeyError, ValueError) as e:
             raise HTTPException(400, str(e))
+        if n_lp >= 0:
+            if not getattr(llm, "supports_logprobs", False):
+                raise HTTPException(400, f"the {getattr(llm, 'provider', 'configured')} backend cannot provide logprobs")
+            rf = dict(rf or {}, logprobs=n_lp)
         mt = body.get("max_tokens") or body.get("max_completion_tokens")
         if mt:
             rf = dict(rf or {}, max_tokens=int(mt))  # per request: the shared llm object is not mutated
@@ -171,13 +206,19 @@ def create_app(llm, model_name: Optional[str] = None, engine=None) -> FastAPI:
         if r.get("tool_calls"):
             msg["tool_calls"] = r["tool_calls"]
         usage = r.get("usage", {})
+        lps = None
+        if n_lp >= 0:
+            if r.get("logprobs") is None:
+                raise HTTPException(500, "the backend returned no logprobs")
+            lps = _wire_logprobs(r["logprobs"])
+        extra = {"logprobs": lps} if lps is not None else {}  # only replies that asked carry the key
         if not body.get("stream"):
             return {"id": cid, "object": "chat.completion", "created": created, "model": name,
-                    "choices": [{"index": 0, "message": msg, "finish_reason": finish}], "usage": usage}
+                    "choices": [{"index": 0, "message": msg, **extra, "finish_reason": finish}], "usage": usage}
 
         def sse():
             first = {"id": cid, "object": "chat.completion.chunk", "created": created, "model": name,
-                     "choices": [{"index": 0, "delta": msg, "finish_reason": None}]}
+                     "choices": [{"index": 0, "delta": msg, **extra, "finish_reason": None}]}
             last = {"id": cid, "object": "chat.completion.chunk", "created": created, "model": name,
                     "choices": [{"index": 0, "delta": {}, "finish_reason": finish}], "usage": usage}
             yield f"data: {json.dumps(first)}\n\n"
