@@ -31,6 +31,10 @@ int pa_token_logprobs(float* out_lp, int out_stride, int* top_ids, float* top_lp
                       const void* logits, int rows, int V, int ld, const int* tokens, const int* lp_n,
                       const int* forced, const int* mask_class, const uint32_t* class_masks, int mask_words,
                       hipStream_t st);
+int pa_apply_penalties(void* logits, int rows, int V, int ld, int* counts, int* distinct, int* n_distinct,
+                       int slots, int cap, const int* pen_slot, const int* pen_reset, const float* presence,
+                       const float* frequency, const int* forced, const int* pair_start, const int* pair_n,
+                       const int* pair_tok, int pair_len, hipStream_t st);
 int pa_tp_topkp_phase(int phase, float* tau, float* ws, const void* logits, int rows, int v_local, int ld,
                       int vocab_offset, int V, const float* temperature, const int* top_k, const float* top_p,
                       const int* mask_class, const uint32_t* class_masks, int mask_words, hipStream_t st);
@@ -706,6 +710,47 @@ void token_logprobs(at::Tensor out_lp, at::Tensor top_ids, at::Tensor top_lp, at
              "token_logprobs");
 }
 
+// Presence / frequency penalties on the logits of the penalised sampling rows (penalties.hip):
+// counts [slots, V], distinct [slots, cap], n_distinct [slots] are the per-slot device state.
+void apply_penalties(at::Tensor logits, at::Tensor counts, at::Tensor distinct, at::Tensor n_distinct,
+                     at::Tensor pen_slot, at::Tensor pen_reset, at::Tensor presence, at::Tensor frequency,
+                     at::Tensor forced, at::Tensor pair_start, at::Tensor pair_n, at::Tensor pair_tok) {
+  check_gpu(counts, "counts"); check_gpu(distinct, "distinct"); check_gpu(n_distinct, "n_distinct");
+  check_gpu(pen_slot, "pen_slot"); check_gpu(pen_reset, "pen_reset"); check_gpu(presence, "presence");
+  check_gpu(frequency, "frequency"); check_gpu(forced, "forced"); check_gpu(pair_start, "pair_start");
+  check_gpu(pair_n, "pair_n"); check_gpu(pair_tok, "pair_tok");
+  check_dtype(counts, at::kInt, "counts"); check_dtype(distinct, at::kInt, "distinct");
+  check_dtype(n_distinct, at::kInt, "n_distinct"); check_dtype(pen_slot, at::kInt, "pen_slot");
+  check_dtype(pen_reset, at::kInt, "pen_reset"); check_dtype(presence, at::kFloat, "presence");
+  check_dtype(frequency, at::kFloat, "frequency"); check_dtype(forced, at::kInt, "forced");
+  check_dtype(pair_start, at::kInt, "pair_start"); check_dtype(pair_n, at::kInt, "pair_n");
+  check_dtype(pair_tok, at::kInt, "pair_tok");
+  TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.scalar_type() == at::kBFloat16 &&
+                  (logits.size(1) == 1 || logits.stride(1) == 1),
+              "logits: [rows, V] bf16 GPU tensor with unit inner stride");
+  const int64_t rows = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(counts.dim() == 2 && counts.size(1) == V, "counts must be [slots, V]");
+  const int64_t slots = counts.size(0);
+  TORCH_CHECK(distinct.dim() == 2 && distinct.size(0) == slots && distinct.size(1) >= 1,
+              "distinct must be [slots, cap]");
+  TORCH_CHECK(n_distinct.numel() == slots, "n_distinct must be [slots]");
+  TORCH_CHECK(slots >= 1 && slots * V < (int64_t(1) << 40), "penalty state too large");
+  TORCH_CHECK(pen_slot.numel() >= rows && pen_reset.numel() >= rows && presence.numel() >= rows &&
+                  frequency.numel() >= rows && forced.numel() >= rows && pair_start.numel() >= rows &&
+                  pair_n.numel() >= rows,
+              "per-row penalty parameter tensors too short");
+  const int64_t ld = rows > 1 ? logits.stride(0) : V;  // a one-row view's stride is arbitrary
+  TORCH_CHECK(ld >= V && rows * ld < (int64_t(1) << 40) && pair_tok.numel() < (int64_t(1) << 31),
+              "logits row stride / pair list out of range");
+  check_rc(pa_apply_penalties(logits.data_ptr(), (int)rows, (int)V, (int)ld, counts.data_ptr<int>(),
+                              distinct.data_ptr<int>(), n_distinct.data_ptr<int>(), (int)slots,
+                              (int)distinct.size(1), pen_slot.data_ptr<int>(), pen_reset.data_ptr<int>(),
+                              presence.data_ptr<float>(), frequency.data_ptr<float>(), forced.data_ptr<int>(),
+                              pair_start.data_ptr<int>(), pair_n.data_ptr<int>(), pair_tok.data_ptr<int>(),
+                              (int)pair_tok.numel(), cur_stream()),
+           "apply_penalties");
+}
+
 int64_t cosine_topk_workspace_bytes(int64_t Q, int64_t N, int64_t K) {
   return pa_cosine_topk_workspace_bytes(Q, N, K);
 }
@@ -1051,6 +1096,9 @@ PYBIND11_MODULE(_C, m) {
   m.def("token_logprobs", &token_logprobs, py::arg("out_lp"), py::arg("top_ids"), py::arg("top_lp"),
         py::arg("workspace"), py::arg("logits"), py::arg("tokens"), py::arg("lp_n"), py::arg("forced"),
         py::arg("mask_class"), py::arg("class_masks"));
+  m.def("apply_penalties", &apply_penalties, py::arg("logits"), py::arg("counts"), py::arg("distinct"),
+        py::arg("n_distinct"), py::arg("pen_slot"), py::arg("pen_reset"), py::arg("presence"),
+        py::arg("frequency"), py::arg("forced"), py::arg("pair_start"), py::arg("pair_n"), py::arg("pair_tok"));
   m.def("tp_topkp_phase", &tp_topkp_phase);
   m.def("cosine_topk_workspace_bytes", &cosine_topk_workspace_bytes);
   m.def("cosine_topk", &cosine_topk);

@@ -181,6 +181,7 @@ PYBIND11_MODULE(_runtime, m) {
         if (d.contains("small_step_part")) c.small_step_part = d["small_step_part"].cast<int32_t>();
         if (d.contains("decode_part_target")) c.decode_part_target = d["decode_part_target"].cast<int32_t>();
         if (d.contains("small_step_target")) c.small_step_target = d["small_step_target"].cast<int32_t>();
+        if (d.contains("penalty_slots")) c.penalty_slots = d["penalty_slots"].cast<int32_t>();
         if (d.contains("eos_ids")) c.eos_ids = d["eos_ids"].cast<std::vector<int32_t>>();
         return std::make_unique<Scheduler>(c);
       }))
@@ -197,6 +198,9 @@ PYBIND11_MODULE(_runtime, m) {
         d["items"] = L.items; d["n_items"] = L.n_items; d["part_size"] = L.part_size;
         d["counts"] = L.counts; d["block_table"] = L.block_table; d["embed_rows"] = L.embed_rows;
         d["lp_n"] = L.lp_n;
+        d["pen_slot"] = L.pen_slot; d["pen_reset"] = L.pen_reset; d["pen_presence"] = L.pen_presence;
+        d["pen_frequency"] = L.pen_frequency; d["pair_start"] = L.pair_start; d["pair_n"] = L.pair_n;
+        d["pair_tok"] = L.pair_tok; d["pair_cap"] = L.pair_cap;
         d["total"] = L.total;
         return d;
       })
@@ -204,14 +208,17 @@ PYBIND11_MODULE(_runtime, m) {
            [](Scheduler& s, int64_t id, const std::vector<int32_t>& prompt, float temperature,
               int32_t max_tokens, int64_t seed, bool ignore_eos,
               const std::vector<int32_t>& stop_ids, const py::object& grammar, int32_t top_k,
-              float top_p, bool embed, bool embed_last, int32_t logprobs) {
+              float top_p, bool embed, bool embed_last, int32_t logprobs, float presence_penalty,
+              float frequency_penalty) {
              s.add_request(id, prompt, temperature, max_tokens, seed, ignore_eos, stop_ids,
-                           make_grammar(grammar), top_k, top_p, embed, embed_last, logprobs);
+                           make_grammar(grammar), top_k, top_p, embed, embed_last, logprobs,
+                           presence_penalty, frequency_penalty);
            },
            py::arg("id"), py::arg("prompt"), py::arg("temperature"), py::arg("max_tokens"),
            py::arg("seed"), py::arg("ignore_eos"), py::arg("stop_ids"), py::arg("grammar"),
            py::arg("top_k") = 0, py::arg("top_p") = 1.0f, py::arg("embed") = false,
-           py::arg("embed_last") = false, py::arg("logprobs") = -1)
+           py::arg("embed_last") = false, py::arg("logprobs") = -1, py::arg("presence_penalty") = 0.0f,
+           py::arg("frequency_penalty") = 0.0f)
       .def("schedule", [](Scheduler& s, uintptr_t buf) {
         py::gil_scoped_release nogil;
         return s.schedule(reinterpret_cast<int32_t*>(buf));
@@ -232,6 +239,7 @@ PYBIND11_MODULE(_runtime, m) {
       .def("abort", &Scheduler::abort)
       .def("take_embed_resets", &Scheduler::take_embed_resets)
       .def("num_free_embed_rows", &Scheduler::num_free_embed_rows)
+      .def_property_readonly("num_free_penalty_slots", &Scheduler::num_free_penalty_slots)
       .def_property_readonly("prefix_defers", &Scheduler::prefix_defers)
       .def_property_readonly("inflight_steps", &Scheduler::inflight_steps)
       .def_property_readonly("spec_rows", &Scheduler::spec_rows)

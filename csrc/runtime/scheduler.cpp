@@ -67,14 +67,24 @@ Scheduler::Scheduler(const SchedulerConfig& cfg)
   L.items = take(4 * L.max_items);
   L.block_table = take(L.max_seqs * L.max_blocks);
   L.embed_rows = take(L.max_tokens);
+  L.pen_slot = take(L.max_seqs);
+  L.pen_reset = take(L.max_seqs);
+  L.pen_presence = take(L.max_seqs);
+  L.pen_frequency = take(L.max_seqs);
+  L.pair_start = take(L.max_seqs);
+  L.pair_n = take(L.max_seqs);
+  L.pair_cap = L.max_tokens + cfg.max_model_len;
+  L.pair_tok = take(L.pair_cap);
   L.total = o;
   for (int32_t r = L.max_seqs; r-- > 0;) embed_free_.push_back(r);
+  for (int32_t r = std::max(0, std::min(cfg.max_num_seqs, cfg.penalty_slots)); r-- > 0;) pen_free_.push_back(r);
 }
 
 void Scheduler::add_request(int64_t id, std::vector<int32_t> prompt, float temperature,
                             int32_t max_tokens, int64_t seed, bool ignore_eos,
                             std::vector<int32_t> stop_ids, std::unique_ptr<Grammar> grammar,
-                            int32_t top_k, float top_p, bool embed, bool embed_last, int32_t logprobs) {
+                            int32_t top_k, float top_p, bool embed, bool embed_last, int32_t logprobs,
+                            float presence_penalty, float frequency_penalty) {
   auto s = std::make_unique<Sequence>();
   s->id = id;
   if ((int32_t)prompt.size() >= cfg_.max_model_len)
@@ -93,6 +103,8 @@ void Scheduler::add_request(int64_t id, std::vector<int32_t> prompt, float tempe
   s->embed = embed;
   s->embed_last = embed && embed_last;
   s->logprobs = embed ? -1 : std::min(logprobs, LOGPROB_TOP);
+  s->presence_penalty = (embed || !std::isfinite(presence_penalty)) ? 0.f : presence_penalty;
+  s->frequency_penalty = (embed || !std::isfinite(frequency_penalty)) ? 0.f : frequency_penalty;
   s->arrival = arrival_counter_++;
   // a grammar that starts with forced text (e.g. '{"key": ') is jump-forwarded into the prompt
   if (s->grammar) {
@@ -188,6 +200,13 @@ int32_t Scheduler::schedule(int32_t* buf) {
   last_plan_.clear();
   int32_t tok_budget = cfg_.max_num_batched_tokens;
   int32_t prefill_budget = cfg_.max_prefill_tokens;
+  // words of the pair region (penalties) the planned sampling rows will take: a penalised row
+  // samples only in a step that carries ALL of its unsent generated tokens
+  int32_t pair_used = 0;
+  auto pair_need = [](const Sequence* s, int32_t n) {
+    return (s->penalised() && s->num_computed + n == (int32_t)s->tokens.size())
+               ? (int32_t)s->tokens.size() - s->prompt_len - s->pen_synced : 0;
+  };
 
   // 1) running sequences: decode tokens, jump-forward runs, unfinished prefill chunks.
   //    With a step in flight (pipelined use), a row that samples in it is continued
@@ -212,6 +231,8 @@ int32_t Scheduler::schedule(int32_t* buf) {
     const int32_t pending = (int32_t)s->tokens.size() - s->num_computed;
     if (pending <= 0 || tok_budget <= 0) continue;
     const int32_t n = std::min(pending, tok_budget);
+    const int32_t pairs = pair_need(s, n);
+    if (pair_used + pairs > L.pair_cap) continue;  // its new tokens do not fit the pair region: next step
     bool ok = ensure_blocks(s, s->num_computed + n);
     while (!ok) {
       // preempt the most recently arrived running sequence that is not yet planned
@@ -233,6 +254,7 @@ int32_t Scheduler::schedule(int32_t* buf) {
     }
     last_plan_.push_back({s, n, !s->embed && s->num_computed + n == (int32_t)s->tokens.size()});
     tok_budget -= n;
+    pair_used += pairs;
   }
   running_.erase(std::remove_if(running_.begin(), running_.end(),
                                 [](Sequence* s) { return !s->running; }),
@@ -282,14 +304,32 @@ int32_t Scheduler::schedule(int32_t* buf) {
       s->embed_slot = embed_free_.back();
       embed_free_.pop_back();
     }
+    // a penalised request without a free penalty slot waits (the requests behind it do not)
+    if (s->penalised() && s->pen_slot < 0 && pen_free_.empty()) {
+      waiting_.pop_front();
+      deferred.push_back(s);
+      continue;
+    }
     if (s->blocks.empty()) match_prefix(s);
     const int32_t pending = (int32_t)s->tokens.size() - s->num_computed;
     const int32_t n = std::min(pending, std::min(tok_budget, prefill_budget));
+    const int32_t pairs = pair_need(s, n);
+    if (pair_used + pairs > L.pair_cap) {  // never with an empty step: one backlog always fits
+      waiting_.pop_front();
+      deferred.push_back(s);
+      continue;
+    }
     const int32_t need =
         (s->num_computed + n + B - 1) / B - (int32_t)s->blocks.size();
     if (need > 0 && bm_.num_free() - need < (running_.empty() ? 0 : watermark)) break;
     if (!ensure_blocks(s, s->num_computed + n)) break;
     waiting_.pop_front();
+    if (s->penalised() && s->pen_slot < 0) {
+      s->pen_slot = pen_free_.back();
+      pen_free_.pop_back();
+      s->pen_fresh = true;
+    }
+    pair_used += pairs;
     s->running = true;
     s->preempted = false;
     running_.push_back(s);
@@ -347,6 +387,17 @@ int32_t Scheduler::schedule(int32_t* buf) {
   int32_t* bt = buf + L.block_table;
   int32_t* er = buf + L.embed_rows;
   int32_t nembed = 0;
+  // penalties: these regions are written only when a planned row is penalised and samples
+  bool any_pen = false;
+  for (const Planned& p : last_plan_) any_pen = any_pen || (p.sample && p.s->penalised());
+  int32_t* psl = buf + L.pen_slot;
+  int32_t* prs = buf + L.pen_reset;
+  float* ppr = reinterpret_cast<float*>(buf + L.pen_presence);
+  float* pfr = reinterpret_cast<float*>(buf + L.pen_frequency);
+  int32_t* pst = buf + L.pair_start;
+  int32_t* pnn = buf + L.pair_n;
+  int32_t* ptk = buf + L.pair_tok;
+  int32_t npen = 0, npair = 0;
   const int32_t tpw = 16 / std::max(1, cfg_.gqa_group);
 
   int32_t T = 0, ns = 0, nsamp = 0, nit = 0, nparted = 0, pslot = 0;
@@ -481,6 +532,30 @@ int32_t Scheduler::schedule(int32_t* buf) {
       seeds[nsamp] = s->seed;
       lpn[nsamp] = s->logprobs;
       if (s->logprobs >= 0) ++nlp;
+      if (any_pen) {
+        psl[nsamp] = -1;
+        prs[nsamp] = 0;
+        ppr[nsamp] = pfr[nsamp] = 0.f;
+        pst[nsamp] = npair;
+        pnn[nsamp] = 0;
+        // a forced row is not penalised and the device reads nothing for it: its backlog
+        // (and the slot's reset) waits for the row's next free sampling step
+        if (s->penalised() && s->pen_slot >= 0 && forced < 0 && !p.spec) {
+          const int32_t from = s->prompt_len + s->pen_synced, upto = (int32_t)s->tokens.size();
+          if (npair + (upto - from) > L.pair_cap)  // the planning above reserved this room
+            throw std::logic_error("scheduler: penalty pair region overflows");
+          psl[nsamp] = s->pen_slot;
+          prs[nsamp] = s->pen_fresh ? 1 : 0;
+          ppr[nsamp] = s->presence_penalty;
+          pfr[nsamp] = s->frequency_penalty;
+          pnn[nsamp] = upto - from;
+          std::memcpy(ptk + npair, s->tokens.data() + from, sizeof(int32_t) * (size_t)(upto - from));
+          npair += upto - from;
+          s->pen_synced = upto - s->prompt_len;
+          s->pen_fresh = false;
+          ++npen;
+        }
+      }
       ++nsamp;
     }
     // attention work items (mirrors pilottai_amd/ops/attn_meta.py)
@@ -557,6 +632,14 @@ int32_t Scheduler::schedule(int32_t* buf) {
     seeds[r] = 0;
     lpn[r] = -1;
   }
+  if (any_pen)
+    for (int32_t r = nsamp; r < L.max_seqs; ++r) {
+      psl[r] = -1;
+      prs[r] = 0;
+      ppr[r] = pfr[r] = 0.f;
+      pst[r] = npair;
+      pnn[r] = 0;
+    }
   for (int32_t r = ns; r < L.max_seqs; ++r) {
     qs[r] = T;
     ql[r] = 0;
@@ -571,7 +654,9 @@ int32_t Scheduler::schedule(int32_t* buf) {
   counts[6] = ntrunc;  // rows that need the top-k / top-p threshold pass
   counts[7] = nembed;  // tokens whose hidden states are pooled (embedding requests)
   counts[8] = nlp;     // rows that need the log-probability pass
-  counts[9] = counts[10] = counts[11] = 0;
+  counts[9] = npen > 0 ? 1 : 0;  // the step has a penalised sampling row (penalty pass)
+  counts[10] = npair;            // words of the pair region those rows use
+  counts[11] = 0;
   if (nit > L.max_items)  // by construction (psz guard above, max_items sizing) this cannot happen
     throw std::logic_error("scheduler: attention item list overflows max_items");
   buf[L.n_items] = nit;
@@ -590,6 +675,8 @@ bool Scheduler::predict(Sequence* s, Planned& e) const {
   const int32_t ng = s->num_generated + 1;
   const int32_t ntok = (int32_t)s->tokens.size() + 1;
   if (ng >= s->max_tokens || ntok >= cfg_.max_model_len) return false;
+  // penalty counts are sent as known tokens: a penalised row waits for its commit
+  if (s->penalised()) return false;
   e.run.clear();
   if (!s->grammar) return true;
   const Grammar& g = *s->grammar;
@@ -627,6 +714,10 @@ SeqOutput Scheduler::finish(Sequence* s, int32_t reason, double now) {
   o.logprobs = s->logprobs;
   o.lp_records = std::move(s->lp_records);
   s->lp_records.clear();
+  if (s->pen_slot >= 0) {  // recycled by the next holder's reset flag
+    pen_free_.push_back(s->pen_slot);
+    s->pen_slot = -1;
+  }
   free_seq(s);
   s->running = false;
   return o;

@@ -77,6 +77,9 @@ struct SchedulerConfig {
   int32_t token_align = 0;
   int32_t kv_heads = 8;                // KV heads per rank (sizes the decode partitioning)
   int32_t align_slack = 96;
+  // device slots for presence / frequency penalty counts (csrc/ops/penalties.hip): a penalised
+  // request holds one from admission to finish; min(max_num_seqs, penalty_slots) exist
+  int32_t penalty_slots = 64;
   std::vector<int32_t> eos_ids;
 };
 
@@ -86,6 +89,16 @@ struct StepLayout {
       offsets, temperature, top_k, top_p, seeds, items, n_items, part_size, counts, block_table, total;
   int32_t lp_n;        // [max_seqs]: alternatives asked per sampling row (log-probabilities), -1 = none
   int32_t embed_rows;  // [max_tokens]: pooling row of each token (embedding requests), max_seqs = none
+  // presence / frequency penalties, after embed_rows: written and copied only by steps with a
+  // penalised sampling row (counts[9] = 1; counts[10] = words of pair_tok in use)
+  int32_t pen_slot;       // [max_seqs]: penalty slot of each sampling row, -1 = none
+  int32_t pen_reset;      // [max_seqs]: 1 = the slot was just taken: clear it first
+  int32_t pen_presence;   // [max_seqs]: fp32 bits
+  int32_t pen_frequency;  // [max_seqs]: fp32 bits
+  int32_t pair_start;     // [max_seqs]: the row's new generated tokens are
+  int32_t pair_n;         // [max_seqs]:   pair_tok[pair_start : pair_start + pair_n]
+  int32_t pair_tok;       // [pair_cap]
+  int32_t pair_cap;       // max_tokens + max_model_len
 };
 
 enum FinishReason : int32_t {
@@ -141,6 +154,14 @@ struct Sequence {
   int64_t seed = 0;
   int32_t logprobs = -1;  // >= 0: log-probability records are kept, with this many alternatives
   std::vector<LogprobRecord> lp_records;  // one per generated token (tokens[prompt_len:])
+  // presence / frequency penalties: the device keeps the counts of tokens[prompt_len:] in
+  // penalty slot pen_slot (held from admission to finish, across preemption); pen_synced of
+  // those tokens have been sent to it; pen_fresh: the slot's old contents are not cleared yet
+  float presence_penalty = 0.f, frequency_penalty = 0.f;
+  int32_t pen_slot = -1;
+  int32_t pen_synced = 0;
+  bool pen_fresh = false;
+  bool penalised() const { return !embed && (presence_penalty != 0.f || frequency_penalty != 0.f); }
   bool ignore_eos = false;
   std::vector<int32_t> stop_ids;
   int64_t arrival = 0;
@@ -174,7 +195,8 @@ class Scheduler {
   void add_request(int64_t id, std::vector<int32_t> prompt, float temperature, int32_t max_tokens,
                    int64_t seed, bool ignore_eos, std::vector<int32_t> stop_ids,
                    std::unique_ptr<Grammar> grammar, int32_t top_k = 0, float top_p = 1.0f,
-                   bool embed = false, bool embed_last = false, int32_t logprobs = -1);
+                   bool embed = false, bool embed_last = false, int32_t logprobs = -1,
+                   float presence_penalty = 0.f, float frequency_penalty = 0.f);
   bool abort(int64_t id);
   // Fill `buf` (layout()) for the next step. Returns the number of tokens in the
   // step (0 = nothing to run).
@@ -222,6 +244,7 @@ class Scheduler {
   };
   std::vector<SeqState> debug_state() const;  // every live sequence (diagnostics)
   int32_t num_free_embed_rows() const { return (int32_t)embed_free_.size(); }
+  int32_t num_free_penalty_slots() const { return (int32_t)pen_free_.size(); }
 
  private:
   bool ensure_blocks(Sequence* s, int32_t upto_tokens);
@@ -262,6 +285,7 @@ class Scheduler {
   std::vector<SeqOutput> aborted_;
   std::vector<int32_t> embed_free_;    // free pooling rows (0 .. max_seqs - 1)
   std::vector<int32_t> embed_resets_;  // rows of preempted embedding requests, to be cleared
+  std::vector<int32_t> pen_free_;      // free penalty slots
   int64_t arrival_counter_ = 0;
   int64_t stat_prompt_tokens_ = 0, stat_cached_tokens_ = 0, stat_preemptions_ = 0, stat_steps_ = 0;
   int64_t stat_aligned_steps_ = 0;

@@ -79,6 +79,9 @@ class LLMConfig(BaseModel):
     temperature: float = Field(default=0.7, ge=0.0, le=2.0)
     top_p: float = Field(default=1.0, gt=0.0, le=1.0)   # nucleus truncation (1 = off)
     top_k: int = Field(default=0, ge=0)                 # top-k truncation (0 = off)
+    # OpenAI penalties over a reply's generated tokens, the request defaults (0 = off)
+    presence_penalty: float = Field(default=0.0, ge=-2.0, le=2.0)
+    frequency_penalty: float = Field(default=0.0, ge=-2.0, le=2.0)
     max_tokens: int = Field(default=2000, gt=0)
     function_calling_model: Optional[str] = None
     system_template: Optional[str] = None

@@ -145,6 +145,10 @@ class EngineConfig:
     # keep every captured hipGraph's node list (torch keep_graph=True) so tools can count its
     # kernels (utils/tracing.py graph_node_counts); costs host memory, off in serving
     keep_graphs: bool = False
+    # device slots for presence / frequency penalty counts: min(max_num_seqs, penalty_slots)
+    # requests with a non-zero penalty run at once, further ones wait for a slot. The state
+    # (slots x vocabulary int32 counts, 33 MB at 64 x 128,256) is allocated on the first such request.
+    penalty_slots: int = 64
 
 
 # TP step header: [op, T, ns, nsamp, bucket, masks_changed, n_copy, truncate, embed]
@@ -205,6 +209,8 @@ class _Request:
     embed: bool = False
     embed_last: bool = False  # last-token pooling (prefix-cache reuse allowed)
     logprobs: int = -1        # -1 off, 0 the chosen token only, 1..20 with that many alternatives
+    presence_penalty: float = 0.0   # OpenAI penalties over the generated tokens, each in [-2, 2]
+    frequency_penalty: float = 0.0
 
 
 class LLMEngine:
@@ -303,6 +309,7 @@ class LLMEngine:
             "small_step_part": int(cfg.small_step_part) if small_step else 0,
             "small_step_target": int(cfg.small_step_target) if small_step else 0,
             "decode_part_target": int(cfg.decode_part_target),
+            "penalty_slots": max(0, min(int(cfg.max_num_seqs), int(cfg.penalty_slots))),
             "eos_ids": list(self.tok.eos_ids)})
         L = self.L = self.sched.layout()
         pin = self.on_gpu
@@ -373,9 +380,15 @@ class LLMEngine:
         self._lp_hosts = [torch.zeros(S, W, dtype=torch.int32, pin_memory=pin) for _ in range(nbuf)]
         self._lp_ws = ops.token_logprobs_workspace(S, self.model.v_local, self.device) \
             if (self.on_gpu and self.tp.size == 1) else None
+        # presence / frequency penalties (submit(presence_penalty=, frequency_penalty=)): per-slot
+        # token counts on the device, allocated on the first penalised request; ops.apply_penalties
+        # rewrites the logits behind the LM head in the step graph's penalty variant
+        self._pen_slots = max(0, min(int(cfg.max_num_seqs), int(cfg.penalty_slots)))
+        self._pen_state = None
         # one graph per (token bucket, top-k/top-p pass, embedding pooling); truncating variants
         # are captured on first use, so steps without truncation pay nothing for it. The variant
-        # with the log-probability pass has the 4-tuple key (bucket, trunc, embed, True).
+        # with the log-probability pass has the 4-tuple key (bucket, trunc, embed, True), a step
+        # with a penalised row the 5-tuple key (bucket, trunc, embed, lp, True).
         self._graphs: Dict[tuple, "torch.cuda.CUDAGraph"] = {}
         self._tau = torch.empty(S, dtype=torch.float32, device=self.device)
         self._graph_pool = None
@@ -464,6 +477,13 @@ class LLMEngine:
         self._offsets = sl("offsets", ms)
         self._seeds = sl("seeds", 2 * ms).view(torch.int64)
         self._lp_n = sl("lp_n", ms)
+        self._pen_slot = sl("pen_slot", ms)
+        self._pen_reset = sl("pen_reset", ms)
+        self._pen_presence = sl("pen_presence", ms).view(torch.float32)
+        self._pen_frequency = sl("pen_frequency", ms).view(torch.float32)
+        self._pair_start = sl("pair_start", ms)
+        self._pair_n = sl("pair_n", ms)
+        self._pair_tok = sl("pair_tok", L["pair_cap"])
 
     def _sync_masks(self) -> bool:
         reg = self.grammar.reg
@@ -484,13 +504,25 @@ class LLMEngine:
                         m.block_table, m.items[:n_it], m.n_items, m.att_counters, m.logit_rows, num_seqs=ns,
                         part_size=m.part_size)
 
+    def _ensure_pen_state(self):
+        """Allocate the penalty slots' device state (engine thread, never inside a capture)."""
+        if self._pen_state is None:
+            self._pen_state = ops.penalty_state(self._pen_slots, self.model.v_local, self.max_model_len,
+                                                self.device)
+
     def _forward_and_sample(self, bucket: int, s_b: int, ns: int, trunc: bool = False, embed: bool = False,
-                            lp: bool = False):
+                            lp: bool = False, pen: bool = False):
         meta = self._meta_for(bucket, s_b, ns)
         if self._async:  # pending tokens of rows that sampled in the previous step
             ops.patch_pending_ids(meta.input_ids[:bucket], self._sampled_dev)
         logits = self.model.forward(meta, self.kv, bucket, s_b, self._part_o, self._part_ml,
                                     embed=(self._embed_rows, self._embed_pool) if embed else None)
+        if pen:
+            # before anything reads the logits: the threshold, the sampler and the logprob pass
+            # all see the penalised distribution
+            ops.apply_penalties(logits, self._pen_state, self._pen_slot[:s_b],
+                                self._pen_reset[:s_b], self._pen_presence[:s_b], self._pen_frequency[:s_b],
+                                self._forced[:s_b], self._pair_start[:s_b], self._pair_n[:s_b], self._pair_tok)
         tau = None
         if trunc:
             # exact top-k / top-p threshold on the full vocabulary; under TP from all-reduced
@@ -527,22 +559,27 @@ class LLMEngine:
                                out=(o_lp[:s_b], o_ids[:s_b], o_lps[:s_b]), workspace=self._lp_ws)
 
     @staticmethod
-    def _graph_key(bucket: int, trunc: bool, embed: bool, lp: bool = False) -> tuple:
+    def _graph_key(bucket: int, trunc: bool, embed: bool, lp: bool = False, pen: bool = False) -> tuple:
+        if pen:
+            return (bucket, trunc, embed, lp, True)
         return (bucket, trunc, embed, True) if lp else (bucket, trunc, embed)
 
-    def _run(self, bucket: int, ns: int, trunc: bool, n_copy: int, embed: bool = False, lp: bool = False):
-        """Replay the (bucket, trunc, embed[, logprobs]) graph — capturing it first if needed — or
-        run eagerly."""
+    def _run(self, bucket: int, ns: int, trunc: bool, n_copy: int, embed: bool = False, lp: bool = False,
+             pen: bool = False):
+        """Replay the (bucket, trunc, embed[, logprobs[, penalties]]) graph — capturing it first if
+        needed — or run eagerly."""
+        if pen:
+            self._ensure_pen_state()
         if not self.use_graphs:
-            self._forward_and_sample(bucket, self._seq_bucket(bucket), ns, trunc, embed, lp)
+            self._forward_and_sample(bucket, self._seq_bucket(bucket), ns, trunc, embed, lp, pen)
             return
-        key = self._graph_key(bucket, trunc, embed, lp)
+        key = self._graph_key(bucket, trunc, embed, lp, pen)
         g = self._graphs.get(key)
         if g is None:
             saved = self._dev_meta[:n_copy].clone()
             pool = self._embed_pool.clone()
             samp = self._sampled_dev.clone()  # the previous step's tokens (pipelined mode)
-            self.capture_graphs([bucket], trunc=trunc, embed=embed, lp=lp)  # clobbers the device metadata
+            self.capture_graphs([bucket], trunc=trunc, embed=embed, lp=lp, pen=pen)  # clobbers the device metadata
             self.stats["graph_captures"] += 1  # a first-use capture inside serving (tens of ms)
             self._dev_meta[:n_copy].copy_(saved)
             self._embed_pool.copy_(pool)
@@ -560,6 +597,7 @@ class LLMEngine:
         d = torch.zeros(L["total"], dtype=torch.int32)
         d[L["slots"]:L["slots"] + L["max_tokens"]] = -1
         d[L["embed_rows"]:L["embed_rows"] + L["max_tokens"]] = L["max_seqs"]
+        d[L["pen_slot"]:L["pen_slot"] + L["max_seqs"]] = -1  # the penalty pass touches nothing
         self._dev_meta.copy_(d.to(self.device))
 
     def capture_embed_graphs(self):
@@ -570,17 +608,19 @@ class LLMEngine:
         self.capture_graphs(embed=True)
 
     def capture_graphs(self, buckets: Optional[Sequence[int]] = None, trunc: bool = False, embed: bool = False,
-                       lp: bool = False):
+                       lp: bool = False, pen: bool = False):
         """Capture one hipGraph per token bucket (shared memory pool); the top-k/top-p,
-        embedding-pooling and log-probability variants are captured on first use."""
+        embedding-pooling, log-probability and penalty variants are captured on first use."""
         if not self.use_graphs:
             return
+        if pen:
+            self._ensure_pen_state()
         self._dummy_meta()
         if self._graph_pool is None:
             self._graph_pool = torch.cuda.graph_pool_handle()
         t0 = time.time()
         for b in sorted(buckets or self.buckets, reverse=True):
-            key = self._graph_key(b, trunc, embed, lp)
+            key = self._graph_key(b, trunc, embed, lp, pen)
             if key in self._graphs:
                 continue
             s_b = self._seq_bucket(b)
@@ -588,11 +628,11 @@ class LLMEngine:
             st.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(st):
                 for _ in range(2):
-                    self._forward_and_sample(b, s_b, 0, trunc, embed, lp)
+                    self._forward_and_sample(b, s_b, 0, trunc, embed, lp, pen)
             torch.cuda.current_stream().wait_stream(st)
             g = torch.cuda.CUDAGraph(keep_graph=True) if self.cfg.keep_graphs else torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, pool=self._graph_pool):
-                self._forward_and_sample(b, s_b, 0, trunc, embed, lp)
+                self._forward_and_sample(b, s_b, 0, trunc, embed, lp, pen)
             if self.cfg.keep_graphs:
                 g.instantiate()
             self._graphs[key] = g
@@ -612,7 +652,8 @@ class LLMEngine:
                temperature: float = 0.7, max_tokens: int = 256, seed: Optional[int] = None,
                ignore_eos: bool = False, stop_ids: Sequence[int] = (), grammar: Optional[list] = None,
                request_id: Optional[int] = None, top_k: int = 0, top_p: float = 1.0,
-               embed: Union[bool, str] = False, logprobs: int = -1) -> int:
+               embed: Union[bool, str] = False, logprobs: int = -1, presence_penalty: float = 0.0,
+               frequency_penalty: float = 0.0) -> int:
         """Thread-safe; `callback` runs on the engine thread when the request finishes.
 
         top_k > 0 / top_p < 1 truncate the (grammar-masked) distribution before
@@ -626,7 +667,14 @@ class LLMEngine:
         logprobs = n: -1 off; 0..20: the output carries, per generated token, its log-probability
         and the n most likely alternatives (GenerationOutput.logprobs) under softmax(logits) over
         the tokens the grammar allowed, at temperature 1 -- whatever temperature / top_k / top_p
-        the token was sampled with. Not for embedding requests, not on a TP > 1 engine."""
+        the token was sampled with. Not for embedding requests, not on a TP > 1 engine.
+
+        presence_penalty a / frequency_penalty b, each in [-2, 2] (OpenAI semantics): at every
+        sampling step, before the grammar mask, top-k / top-p, the sampler and the logprob pass,
+        logit[t] -= a * [c_t > 0] + b * c_t with c_t the occurrences of t among the request's
+        generated tokens so far (sampled and grammar-forced; the prompt is not counted). Both 0:
+        the request is exactly what it is without them. Not for embedding requests, not on a
+        TP > 1 engine, not with async_steps."""
         if self._err is not None:
             raise RuntimeError(f"engine failed: {self._err!r}")
         logprobs = -1 if logprobs is None else int(logprobs)
@@ -636,13 +684,28 @@ class LLMEngine:
             raise ValueError("logprobs are not available on embedding requests")
         if logprobs >= 0 and self.tp.size > 1:
             raise ValueError("logprobs are not supported on a tensor-parallel (TP > 1) engine")
+        pens = []
+        for name, v in (("presence_penalty", presence_penalty), ("frequency_penalty", frequency_penalty)):
+            v = 0.0 if v is None else v
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not -2.0 <= v <= 2.0:  # NaN fails too
+                raise ValueError(f"{name} must be a number in [-2, 2], not {v!r}")
+            pens.append(float(v))
+        if pens[0] != 0.0 or pens[1] != 0.0:
+            if embed:
+                raise ValueError("penalties are not available on embedding requests")
+            if self.tp.size > 1:
+                raise ValueError("penalties are not supported on a tensor-parallel (TP > 1) engine")
+            if self.cfg.async_steps:
+                raise ValueError("penalties are not supported on an async_steps engine")
+            if self._pen_slots < 1:
+                raise ValueError("penalties need EngineConfig.penalty_slots >= 1")
         rid = request_id if request_id is not None else self.new_request_id()
         if seed is None:
             seed = (self.cfg.seed * 0x9E3779B1 + rid * 0x85EBCA77) & 0x7FFFFFFFFFFFFFFF
         req = _Request(rid, list(prompt_ids), float(temperature), int(max_tokens), int(seed),
                        bool(ignore_eos), list(stop_ids), grammar, callback, self._rt.now(),
                        int(top_k or 0), float(1.0 if top_p is None else top_p), bool(embed), embed == "last",
-                       logprobs)
+                       logprobs, pens[0], pens[1])
         self._inbox.put(req)
         self._wake.set()
         return rid
@@ -874,7 +937,7 @@ class LLMEngine:
             self._reqs[req.rid] = req
             self.sched.add_request(req.rid, req.prompt_ids, req.temperature, req.max_tokens, req.seed,
                                    req.ignore_eos, req.stop_ids, req.grammar, req.top_k, req.top_p, req.embed,
-                                   req.embed_last, req.logprobs)
+                                   req.embed_last, req.logprobs, req.presence_penalty, req.frequency_penalty)
             self.stats["requests"] += 1
         while True:
             try:
@@ -932,12 +995,15 @@ class LLMEngine:
             if self.sched.num_running == 0 and self.sched.num_waiting > 0:
                 raise RuntimeError("KV cache too small for the head request")
             return False
-        c = self._host_np[L["counts"]:L["counts"] + 9]
+        c = self._host_np[L["counts"]:L["counts"] + 11]
         ns, nsamp, trunc, embed, lp = int(c[1]), int(c[2]), int(c[6]) > 0, int(c[7]) > 0, int(c[8]) > 0
+        pen = int(c[9]) > 0
         bucket = next(b for b in self.buckets if b >= T)
         s_b = self._seq_bucket(bucket)
         masks_changed = self._sync_masks()
         n_copy = L["embed_rows"] + bucket if embed else L["block_table"] + ns * L["max_blocks"]
+        if pen:  # up to the end of the pair words the step's penalised rows use
+            n_copy = L["pair_tok"] + int(c[10])
         resets = self.sched.take_embed_resets()
         if resets:  # preempted embedding requests restart from token 0
             self._embed_pool[torch.tensor(resets, dtype=torch.long, device=self.device)] = 0.0
@@ -949,7 +1015,7 @@ class LLMEngine:
                 self.tp.broadcast(self._class_masks)
             self.tp.broadcast(self._dev_meta[:n_copy])
         with torch.inference_mode(), trace_range("engine.forward"):
-            self._run(bucket, ns, trunc, n_copy, embed, lp)
+            self._run(bucket, ns, trunc, n_copy, embed, lp, pen)
         if self._step_listeners:
             self._notify_launch(T)
         if nsamp:

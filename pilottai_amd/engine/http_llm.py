@@ -13,6 +13,8 @@ Structured replies: agents pass `response_format={"schema": <rules.yaml name>,
 OpenAI-compatible server, pass `schema_mode="json_object"` to send
 `{"type": "json_object"}` instead. `response_format["logprobs"] = n` (0..20) is sent as
 `logprobs: true, top_logprobs: n`; the reply's `logprobs.content` comes back as `r["logprobs"]`.
+`response_format["presence_penalty"]` / `["frequency_penalty"]` (or the `LLMConfig` defaults of
+the same names) are sent under their OpenAI names when non-zero.
 
     LLMConfig(provider="openai", base_url="http://10.0.0.5:8000/v1", api_key=...)
 """
@@ -26,6 +28,7 @@ from .local_llm import BaseLLM, _cfg_get
 class OpenAICompatLLM(BaseLLM):
     provider = "openai"
     supports_logprobs = True
+    supports_penalties = True
 
     def __init__(self, config: Any = None, base_url: Optional[str] = None, timeout_s: float = 600.0,
                  schema_mode: str = "pilottai"):
@@ -62,6 +65,10 @@ class OpenAICompatLLM(BaseLLM):
         if rf.get("logprobs") is not None and int(rf["logprobs"]) >= 0:
             body["logprobs"] = True
             body["top_logprobs"] = int(rf["logprobs"])
+        for k in ("presence_penalty", "frequency_penalty"):
+            v = rf.get(k, getattr(self, k))
+            if v:
+                body[k] = float(v)
         if tools:
             body["tools"] = self._format_tools(tools)
         elif rf.get("schema") is not None:

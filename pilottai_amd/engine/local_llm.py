@@ -110,6 +110,8 @@ class BaseLLM:
 
     provider = "base"
     supports_logprobs = False  # response_format["logprobs"] is honoured and r["logprobs"] returned
+    # response_format["presence_penalty"] / ["frequency_penalty"] are honoured
+    supports_penalties = False
 
     def __init__(self, config: Any = None):
         self.config = config
@@ -117,6 +119,9 @@ class BaseLLM:
         self.temperature = float(_cfg_get(config, "temperature", 0.7))
         self.top_p = float(_cfg_get(config, "top_p", 1.0))
         self.top_k = int(_cfg_get(config, "top_k", 0))
+        # request defaults of the OpenAI penalties over the generated tokens (0 = off)
+        self.presence_penalty = float(_cfg_get(config, "presence_penalty", 0.0) or 0.0)
+        self.frequency_penalty = float(_cfg_get(config, "frequency_penalty", 0.0) or 0.0)
         self.max_tokens = int(_cfg_get(config, "max_tokens", 2000))
         self.retry_attempts = max(1, int(_cfg_get(config, "retry_attempts", 3)))
         self.retry_delay = float(_cfg_get(config, "retry_delay", 1.0))
@@ -189,6 +194,7 @@ class LocalLLM(BaseLLM):
 
     provider = "local"
     supports_logprobs = True
+    supports_penalties = True
     prefix_cache_layout = True  # agents put the shared task text first (core/agent.py)
 
     def __init__(self, config: Any = None, engine=None):
@@ -232,7 +238,9 @@ class LocalLLM(BaseLLM):
                                  grammar=grammar,
                                  seed=rf.get("seed"), top_k=int(rf.get("top_k", self.top_k)),
                                  top_p=float(rf.get("top_p", self.top_p)),
-                                 logprobs=-1 if rf.get("logprobs") is None else int(rf["logprobs"]))
+                                 logprobs=-1 if rf.get("logprobs") is None else int(rf["logprobs"]),
+                                 presence_penalty=rf.get("presence_penalty", self.presence_penalty),
+                                 frequency_penalty=rf.get("frequency_penalty", self.frequency_penalty))
         try:
             out = await fut
         except asyncio.CancelledError:

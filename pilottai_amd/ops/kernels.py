@@ -241,6 +241,37 @@ def token_logprobs(logits, tokens, lp_n, forced, mask_class, class_masks, out=No
     return out
 
 
+PENALTY_LAUNCHES = 1  # kernels apply_penalties() launches on the GPU
+
+
+def penalty_state(slots: int, V: int, cap: int, device):
+    """Zeroed device state of `slots` penalty slots: (counts int32 [slots, V], distinct int32
+    [slots, cap] -- the tokens whose count is non-zero -- and n_distinct int32 [slots])."""
+    return (torch.zeros(slots, V, dtype=torch.int32, device=device),
+            torch.zeros(slots, cap, dtype=torch.int32, device=device),
+            torch.zeros(slots, dtype=torch.int32, device=device))
+
+
+def apply_penalties(logits, state, pen_slot, pen_reset, presence, frequency, forced, pair_start, pair_n,
+                    pair_tok):
+    """Presence / frequency penalties, in place on `logits` [rows, V] bf16 (csrc/ops/penalties.hip).
+
+    Row r with slot s = pen_slot[r] >= 0 and forced[r] < 0: if pen_reset[r], the slot's counts
+    are cleared first; the tokens pair_tok[pair_start[r] : pair_start[r] + pair_n[r]] are added
+    to the slot's counts; then every token t with count c > 0 gets
+    logit[t] <- bf16(float(logit[t]) - (presence[r] + frequency[r] * c)), fp32 arithmetic, one
+    round-to-nearest-even conversion. Every other row, and the state of its slot, is untouched.
+    `state` = penalty_state(...), updated in place. A slot may appear in one row only."""
+    counts, distinct, n_distinct = state
+    if _on_gpu(logits):
+        require_native().apply_penalties(logits, counts, distinct, n_distinct, pen_slot, pen_reset, presence,
+                                         frequency, forced, pair_start, pair_n, pair_tok)
+        return logits
+    ref.apply_penalties(logits, state, pen_slot, pen_reset, presence, frequency, forced, pair_start, pair_n,
+                        pair_tok)
+    return logits
+
+
 COSINE_MAX_Q = 64  # queries per index pass (LDS-resident query tiles)
 
 

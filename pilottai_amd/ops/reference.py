@@ -273,6 +273,50 @@ def token_logprobs(logits: torch.Tensor, tokens, lp_n, forced, mask_class, class
     return out_lp, out_ids, out_lps
 
 
+def apply_penalties(logits: torch.Tensor, state, pen_slot, pen_reset, presence, frequency, forced,
+                    pair_start, pair_n, pair_tok):
+    """Presence / frequency penalties in place on `logits` [rows, V] (see ops.apply_penalties),
+    with the device kernel's data flow: the slot's distinct list is walked to clear it, the
+    row's new tokens are counted and appended on their first occurrence, and the logits of the
+    listed tokens are rewritten in fp32 with one conversion back to the logits' dtype."""
+    counts, distinct, n_distinct = state
+    rows, V = logits.shape
+    slots, cap = distinct.shape
+    for r in range(rows):
+        s = int(pen_slot[r])
+        if s < 0 or s >= slots or int(forced[r]) >= 0:
+            continue
+        if int(pen_reset[r]) != 0:
+            n_old = min(max(int(n_distinct[s]), 0), cap)
+            for t in distinct[s, :n_old].tolist():
+                if 0 <= t < V:
+                    counts[s, t] = 0
+            n_distinct[s] = 0
+        a0, n_new = int(pair_start[r]), int(pair_n[r])
+        if a0 < 0 or n_new < 0 or a0 + n_new > pair_tok.numel():
+            n_new = 0
+        for t in pair_tok[a0:a0 + n_new].tolist():
+            if not 0 <= t < V:
+                continue
+            if int(counts[s, t]) == 0:
+                at = int(n_distinct[s])
+                if at < cap:
+                    distinct[s, at] = t
+                n_distinct[s] = at + 1
+            counts[s, t] += 1
+        n = min(max(int(n_distinct[s]), 0), cap)
+        if n == 0:
+            continue
+        idx = distinct[s, :n].long()
+        idx = idx[(idx >= 0) & (idx < V)]
+        c = counts[s, idx]
+        idx, c = idx[c > 0], c[c > 0].float()
+        a = presence[r].float()
+        b = frequency[r].float()
+        logits[r, idx] = (logits[r, idx].float() - (a + b * c)).to(logits.dtype)
+    return logits
+
+
 # ---------------------------------------------------------------------------
 # semantic index
 # ---------------------------------------------------------------------------

@@ -26,6 +26,11 @@ generated token its log-probability and the most likely alternatives, under soft
 over the tokens the reply's grammar allowed at that position, at temperature 1 (a
 grammar-forced token has 0.0). Each entry also carries `token_id`; -inf is sent as -9999.0.
 
+`presence_penalty` / `frequency_penalty` (numbers in [-2, 2], OpenAI semantics over the
+GENERATED tokens: logit[t] -= presence * [c_t > 0] + frequency * c_t) are applied by the engine
+before the grammar mask, top-k / top-p, the sampler and the logprob pass; 0 or absent means
+nothing. `logit_bias`, a multiplicative `repetition_penalty` and `n > 1` are not supported.
+
 Every request becomes one `LocalLLM` call, i.e. one sequence in the engine's continuous
 batch. Concurrent HTTP clients share the engine's steps exactly like in-process agents.
 
@@ -113,6 +118,20 @@ def _response_format(body: Dict[str, Any]) -> Optional[Dict[str, Any]]:
     return out
 
 
+def _penalties(body: Dict[str, Any]) -> Dict[str, float]:
+    """The request's non-zero `presence_penalty` / `frequency_penalty` (0 or absent: nothing)."""
+    out: Dict[str, float] = {}
+    for k in ("presence_penalty", "frequency_penalty"):
+        v = body.get(k)
+        if v is None:
+            continue
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not -2.0 <= v <= 2.0:  # NaN fails too
+            raise ValueError(f"{k} must be a number between -2 and 2")
+        if v != 0:
+            out[k] = float(v)
+    return out
+
+
 def _logprobs(body: Dict[str, Any]) -> int:
     """The number of alternatives asked for (-1: no logprobs), from `logprobs` / `top_logprobs`."""
     want, top = body.get("logprobs"), body.get("top_logprobs")
@@ -186,8 +205,14 @@ def create_app(llm, model_name: Optional[str] = None, engine=None) -> FastAPI:
             rf = _response_format(body)
             tools = _tools(body)
             n_lp = _logprobs(body)
+            pens = _penalties(body)
         except (KeyError, ValueError) as e:
             raise HTTPException(400, str(e))
+        if pens:
+            if not getattr(llm, "supports_penalties", False):
+                raise HTTPException(400, f"the {getattr(llm, 'provider', 'configured')} backend cannot apply "
+                                         "presence / frequency penalties")
+            rf = dict(rf or {}, **pens)
         if n_lp >= 0:
             if not getattr(llm, "supports_logprobs", False):
                 raise HTTPException(400, f"the {getattr(llm, 'provider', 'configured')} backend cannot provide logprobs")
