@@ -35,6 +35,13 @@ int pa_apply_penalties(void* logits, int rows, int V, int ld, int* counts, int* 
                        int slots, int cap, const int* pen_slot, const int* pen_reset, const float* presence,
                        const float* frequency, const int* forced, const int* pair_start, const int* pair_n,
                        const int* pair_tok, int pair_len, hipStream_t st);
+int pa_apply_logit_bias(void* logits, int rows, int V, int ld, const int* bias_start, const int* bias_n,
+                        const int* bias_tok, const float* bias_val, int bias_len, const int* forced,
+                        hipStream_t st);
+int pa_minp_threshold(float* tau, int has_tau, const void* logits, int rows, int V, int ld,
+                      const float* temperature, const float* min_p, const float* ln_min_p, const int* forced,
+                      const int* mask_class, const uint32_t* class_masks, int mask_words, int n_classes,
+                      hipStream_t st);
 int pa_tp_topkp_phase(int phase, float* tau, float* ws, const void* logits, int rows, int v_local, int ld,
                       int vocab_offset, int V, const float* temperature, const int* top_k, const float* top_p,
                       const int* mask_class, const uint32_t* class_masks, int mask_words, hipStream_t st);
@@ -751,6 +758,62 @@ void apply_penalties(at::Tensor logits, at::Tensor counts, at::Tensor distinct, 
            "apply_penalties");
 }
 
+// logit_bias on the logits of the sampling rows (logit_shaping.hip): row r adds bias_val[i] to
+// logit[bias_tok[i]] for i in [bias_start[r], bias_start[r] + bias_n[r]).
+void apply_logit_bias(at::Tensor logits, at::Tensor bias_start, at::Tensor bias_n, at::Tensor bias_tok,
+                      at::Tensor bias_val, at::Tensor forced) {
+  check_gpu(bias_start, "bias_start"); check_gpu(bias_n, "bias_n"); check_gpu(bias_tok, "bias_tok");
+  check_gpu(bias_val, "bias_val"); check_gpu(forced, "forced");
+  check_dtype(bias_start, at::kInt, "bias_start"); check_dtype(bias_n, at::kInt, "bias_n");
+  check_dtype(bias_tok, at::kInt, "bias_tok"); check_dtype(bias_val, at::kFloat, "bias_val");
+  check_dtype(forced, at::kInt, "forced");
+  TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.scalar_type() == at::kBFloat16 &&
+                  (logits.size(1) == 1 || logits.stride(1) == 1),
+              "logits: [rows, V] bf16 GPU tensor with unit inner stride");
+  const int64_t rows = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(bias_start.numel() >= rows && bias_n.numel() >= rows && forced.numel() >= rows,
+              "per-row bias parameter tensors too short");
+  TORCH_CHECK(bias_val.numel() >= bias_tok.numel() && bias_tok.numel() < (int64_t(1) << 31),
+              "bias_val must be as long as bias_tok");
+  const int64_t ld = rows > 1 ? logits.stride(0) : V;  // a one-row view's stride is arbitrary
+  TORCH_CHECK(V > 0 && V < (int64_t(1) << 31) && ld >= V && rows * ld < (int64_t(1) << 40),
+              "logits row stride out of range");
+  check_rc(pa_apply_logit_bias(logits.data_ptr(), (int)rows, (int)V, (int)ld, bias_start.data_ptr<int>(),
+                               bias_n.data_ptr<int>(), bias_tok.data_ptr<int>(), bias_val.data_ptr<float>(),
+                               (int)bias_tok.numel(), forced.data_ptr<int>(), cur_stream()),
+           "apply_logit_bias");
+}
+
+// min_p threshold of the sampling rows (logit_shaping.hip): tau[r] = max(tau[r], tau_mp) when
+// has_tau (tau holds the step's top-k / top-p thresholds), else tau[r] = tau_mp or -inf.
+void minp_threshold(at::Tensor tau, bool has_tau, at::Tensor logits, at::Tensor temperature, at::Tensor min_p,
+                    at::Tensor ln_min_p, at::Tensor forced, at::Tensor mask_class, at::Tensor class_masks) {
+  for (auto* t : {&tau, &temperature, &min_p, &ln_min_p, &forced, &mask_class, &class_masks})
+    check_gpu(*t, "minp_threshold arg");
+  check_dtype(tau, at::kFloat, "tau"); check_dtype(logits, at::kBFloat16, "logits");
+  check_dtype(temperature, at::kFloat, "temperature"); check_dtype(min_p, at::kFloat, "min_p");
+  check_dtype(ln_min_p, at::kFloat, "ln_min_p"); check_dtype(forced, at::kInt, "forced");
+  check_dtype(mask_class, at::kInt, "mask_class"); check_dtype(class_masks, at::kInt, "class_masks");
+  TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 && (logits.size(1) == 1 || logits.stride(1) == 1),
+              "logits: [rows, V] bf16 GPU tensor with unit inner stride");
+  const int64_t rows = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(tau.is_contiguous() && tau.numel() >= rows && temperature.numel() >= rows &&
+                  min_p.numel() >= rows && ln_min_p.numel() >= rows && forced.numel() >= rows &&
+                  mask_class.numel() >= rows,
+              "per-row min_p parameter tensors too short");
+  const int64_t ld = rows > 1 ? logits.stride(0) : V;  // a one-row view's stride is arbitrary
+  TORCH_CHECK(V > 0 && V < (int64_t(1) << 31) && ld >= V && rows * ld < (int64_t(1) << 40),
+              "logits row stride out of range");
+  TORCH_CHECK(class_masks.dim() == 2 && class_masks.is_contiguous() && class_masks.size(1) * 32 >= V,
+              "class_masks must be [classes, words] and cover the vocabulary");
+  check_rc(pa_minp_threshold(tau.data_ptr<float>(), has_tau ? 1 : 0, logits.data_ptr(), (int)rows, (int)V,
+                             (int)ld, temperature.data_ptr<float>(), min_p.data_ptr<float>(),
+                             ln_min_p.data_ptr<float>(), forced.data_ptr<int>(), mask_class.data_ptr<int>(),
+                             reinterpret_cast<const uint32_t*>(class_masks.data_ptr<int>()),
+                             (int)class_masks.size(1), (int)class_masks.size(0), cur_stream()),
+           "minp_threshold");
+}
+
 int64_t cosine_topk_workspace_bytes(int64_t Q, int64_t N, int64_t K) {
   return pa_cosine_topk_workspace_bytes(Q, N, K);
 }
@@ -1099,6 +1162,11 @@ PYBIND11_MODULE(_C, m) {
   m.def("apply_penalties", &apply_penalties, py::arg("logits"), py::arg("counts"), py::arg("distinct"),
         py::arg("n_distinct"), py::arg("pen_slot"), py::arg("pen_reset"), py::arg("presence"),
         py::arg("frequency"), py::arg("forced"), py::arg("pair_start"), py::arg("pair_n"), py::arg("pair_tok"));
+  m.def("apply_logit_bias", &apply_logit_bias, py::arg("logits"), py::arg("bias_start"), py::arg("bias_n"),
+        py::arg("bias_tok"), py::arg("bias_val"), py::arg("forced"));
+  m.def("minp_threshold", &minp_threshold, py::arg("tau"), py::arg("has_tau"), py::arg("logits"),
+        py::arg("temperature"), py::arg("min_p"), py::arg("ln_min_p"), py::arg("forced"),
+        py::arg("mask_class"), py::arg("class_masks"));
   m.def("tp_topkp_phase", &tp_topkp_phase);
   m.def("cosine_topk_workspace_bytes", &cosine_topk_workspace_bytes);
   m.def("cosine_topk", &cosine_topk);

@@ -201,6 +201,8 @@ PYBIND11_MODULE(_runtime, m) {
         d["pen_slot"] = L.pen_slot; d["pen_reset"] = L.pen_reset; d["pen_presence"] = L.pen_presence;
         d["pen_frequency"] = L.pen_frequency; d["pair_start"] = L.pair_start; d["pair_n"] = L.pair_n;
         d["pair_tok"] = L.pair_tok; d["pair_cap"] = L.pair_cap;
+        d["bias_start"] = L.bias_start; d["bias_n"] = L.bias_n; d["minp"] = L.minp; d["ln_minp"] = L.ln_minp;
+        d["bias_tok"] = L.bias_tok; d["bias_val"] = L.bias_val; d["bias_cap"] = L.bias_cap;
         d["total"] = L.total;
         return d;
       })
@@ -209,16 +211,19 @@ PYBIND11_MODULE(_runtime, m) {
               int32_t max_tokens, int64_t seed, bool ignore_eos,
               const std::vector<int32_t>& stop_ids, const py::object& grammar, int32_t top_k,
               float top_p, bool embed, bool embed_last, int32_t logprobs, float presence_penalty,
-              float frequency_penalty) {
+              float frequency_penalty, const std::vector<std::pair<int32_t, float>>& logit_bias,
+              float min_p, float ln_min_p) {
              s.add_request(id, prompt, temperature, max_tokens, seed, ignore_eos, stop_ids,
                            make_grammar(grammar), top_k, top_p, embed, embed_last, logprobs,
-                           presence_penalty, frequency_penalty);
+                           presence_penalty, frequency_penalty, logit_bias, min_p, ln_min_p);
            },
            py::arg("id"), py::arg("prompt"), py::arg("temperature"), py::arg("max_tokens"),
            py::arg("seed"), py::arg("ignore_eos"), py::arg("stop_ids"), py::arg("grammar"),
            py::arg("top_k") = 0, py::arg("top_p") = 1.0f, py::arg("embed") = false,
            py::arg("embed_last") = false, py::arg("logprobs") = -1, py::arg("presence_penalty") = 0.0f,
-           py::arg("frequency_penalty") = 0.0f)
+           py::arg("frequency_penalty") = 0.0f,
+           py::arg("logit_bias") = std::vector<std::pair<int32_t, float>>{}, py::arg("min_p") = 0.0f,
+           py::arg("ln_min_p") = 0.0f)
       .def("schedule", [](Scheduler& s, uintptr_t buf) {
         py::gil_scoped_release nogil;
         return s.schedule(reinterpret_cast<int32_t*>(buf));

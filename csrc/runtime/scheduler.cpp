@@ -75,6 +75,13 @@ Scheduler::Scheduler(const SchedulerConfig& cfg)
   L.pair_n = take(L.max_seqs);
   L.pair_cap = L.max_tokens + cfg.max_model_len;
   L.pair_tok = take(L.pair_cap);
+  L.bias_start = take(L.max_seqs);
+  L.bias_n = take(L.max_seqs);
+  L.minp = take(L.max_seqs);
+  L.ln_minp = take(L.max_seqs);
+  L.bias_cap = L.max_seqs * LOGIT_BIAS_MAX;
+  L.bias_tok = take(L.bias_cap);
+  L.bias_val = take(L.bias_cap);
   L.total = o;
   for (int32_t r = L.max_seqs; r-- > 0;) embed_free_.push_back(r);
   for (int32_t r = std::max(0, std::min(cfg.max_num_seqs, cfg.penalty_slots)); r-- > 0;) pen_free_.push_back(r);
@@ -84,7 +91,9 @@ void Scheduler::add_request(int64_t id, std::vector<int32_t> prompt, float tempe
                             int32_t max_tokens, int64_t seed, bool ignore_eos,
                             std::vector<int32_t> stop_ids, std::unique_ptr<Grammar> grammar,
                             int32_t top_k, float top_p, bool embed, bool embed_last, int32_t logprobs,
-                            float presence_penalty, float frequency_penalty) {
+                            float presence_penalty, float frequency_penalty,
+                            std::vector<std::pair<int32_t, float>> logit_bias, float min_p,
+                            float ln_min_p) {
   auto s = std::make_unique<Sequence>();
   s->id = id;
   if ((int32_t)prompt.size() >= cfg_.max_model_len)
@@ -105,6 +114,29 @@ void Scheduler::add_request(int64_t id, std::vector<int32_t> prompt, float tempe
   s->logprobs = embed ? -1 : std::min(logprobs, LOGPROB_TOP);
   s->presence_penalty = (embed || !std::isfinite(presence_penalty)) ? 0.f : presence_penalty;
   s->frequency_penalty = (embed || !std::isfinite(frequency_penalty)) ? 0.f : frequency_penalty;
+  if (!embed) {
+    // the device pass wants unique ids per row: sorted by id, the first entry of an id kept
+    logit_bias.erase(std::remove_if(logit_bias.begin(), logit_bias.end(),
+                                    [](const std::pair<int32_t, float>& e) {
+                                      return e.first < 0 || e.second == 0.f || !std::isfinite(e.second);
+                                    }),
+                     logit_bias.end());
+    std::stable_sort(logit_bias.begin(), logit_bias.end(),
+                     [](const std::pair<int32_t, float>& a, const std::pair<int32_t, float>& b) {
+                       return a.first < b.first;
+                     });
+    logit_bias.erase(std::unique(logit_bias.begin(), logit_bias.end(),
+                                 [](const std::pair<int32_t, float>& a, const std::pair<int32_t, float>& b) {
+                                   return a.first == b.first;
+                                 }),
+                     logit_bias.end());
+    if ((int32_t)logit_bias.size() > LOGIT_BIAS_MAX) logit_bias.resize(LOGIT_BIAS_MAX);
+    s->logit_bias = std::move(logit_bias);
+    if (min_p > 0.f && min_p <= 1.f && std::isfinite(ln_min_p) && ln_min_p <= 0.f) {
+      s->min_p = min_p;
+      s->ln_min_p = ln_min_p;
+    }
+  }
   s->arrival = arrival_counter_++;
   // a grammar that starts with forced text (e.g. '{"key": ') is jump-forwarded into the prompt
   if (s->grammar) {
@@ -398,6 +430,16 @@ int32_t Scheduler::schedule(int32_t* buf) {
   int32_t* pnn = buf + L.pair_n;
   int32_t* ptk = buf + L.pair_tok;
   int32_t npen = 0, npair = 0;
+  // logit_bias / min_p: these regions are written only when a planned sampling row is shaped
+  bool any_shape = false;
+  for (const Planned& p : last_plan_) any_shape = any_shape || (p.sample && p.s->shaped());
+  int32_t* bst = buf + L.bias_start;
+  int32_t* bnn = buf + L.bias_n;
+  float* bmp = reinterpret_cast<float*>(buf + L.minp);
+  float* bln = reinterpret_cast<float*>(buf + L.ln_minp);
+  int32_t* btk = buf + L.bias_tok;
+  float* bvl = reinterpret_cast<float*>(buf + L.bias_val);
+  int32_t nbias = 0;
   const int32_t tpw = 16 / std::max(1, cfg_.gqa_group);
 
   int32_t T = 0, ns = 0, nsamp = 0, nit = 0, nparted = 0, pslot = 0;
@@ -556,6 +598,23 @@ int32_t Scheduler::schedule(int32_t* buf) {
           ++npen;
         }
       }
+      if (any_shape) {
+        // stateless: every sampling row of a shaped sequence carries the request's list and
+        // min_p -- speculative rows and rows after a preemption alike; the device skips a
+        // forced row by itself
+        const int32_t nb = s->shaped() ? (int32_t)s->logit_bias.size() : 0;
+        if (nbias + nb > L.bias_cap)  // max_seqs rows of at most LOGIT_BIAS_MAX entries each
+          throw std::logic_error("scheduler: logit_bias region overflows");
+        bst[nsamp] = nbias;
+        bnn[nsamp] = nb;
+        bmp[nsamp] = s->shaped() ? s->min_p : 0.f;
+        bln[nsamp] = s->shaped() ? s->ln_min_p : 0.f;
+        for (int32_t j = 0; j < nb; ++j) {
+          btk[nbias + j] = s->logit_bias[j].first;
+          bvl[nbias + j] = s->logit_bias[j].second;
+        }
+        nbias += nb;
+      }
       ++nsamp;
     }
     // attention work items (mirrors pilottai_amd/ops/attn_meta.py)
@@ -640,6 +699,12 @@ int32_t Scheduler::schedule(int32_t* buf) {
       pst[r] = npair;
       pnn[r] = 0;
     }
+  if (any_shape)
+    for (int32_t r = nsamp; r < L.max_seqs; ++r) {
+      bst[r] = nbias;
+      bnn[r] = 0;
+      bmp[r] = bln[r] = 0.f;
+    }
   for (int32_t r = ns; r < L.max_seqs; ++r) {
     qs[r] = T;
     ql[r] = 0;
@@ -656,7 +721,7 @@ int32_t Scheduler::schedule(int32_t* buf) {
   counts[8] = nlp;     // rows that need the log-probability pass
   counts[9] = npen > 0 ? 1 : 0;  // the step has a penalised sampling row (penalty pass)
   counts[10] = npair;            // words of the pair region those rows use
-  counts[11] = 0;
+  counts[11] = any_shape ? 1 + nbias : 0;  // a shaped sampling row (logit_bias / min_p pass) + its bias words
   if (nit > L.max_items)  // by construction (psz guard above, max_items sizing) this cannot happen
     throw std::logic_error("scheduler: attention item list overflows max_items");
   buf[L.n_items] = nit;

@@ -17,6 +17,7 @@
 #include <memory>
 #include <string>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 #include "block_manager.h"
@@ -99,7 +100,19 @@ struct StepLayout {
   int32_t pair_n;         // [max_seqs]:   pair_tok[pair_start : pair_start + pair_n]
   int32_t pair_tok;       // [pair_cap]
   int32_t pair_cap;       // max_tokens + max_model_len
+  // logit_bias / min_p ("shaped" rows, csrc/ops/logit_shaping.hip), after the penalty regions:
+  // written and copied only by steps with a shaped sampling row. counts[11] (the header's one
+  // free word) = 0 in every other step, else 1 + the words of bias_tok / bias_val in use.
+  int32_t bias_start;  // [max_seqs]: the row's bias list is entries
+  int32_t bias_n;      // [max_seqs]:   [bias_start, bias_start + bias_n) of bias_tok / bias_val
+  int32_t minp;        // [max_seqs]: fp32 bits of min_p, 0 = off
+  int32_t ln_minp;     // [max_seqs]: fp32 bits of float32(ln min_p), as submitted
+  int32_t bias_tok;    // [bias_cap]
+  int32_t bias_val;    // [bias_cap]: fp32 bits
+  int32_t bias_cap;    // max_seqs * LOGIT_BIAS_MAX: a step's lists always fit
 };
+
+constexpr int32_t LOGIT_BIAS_MAX = 300;  // entries of one request's logit_bias
 
 enum FinishReason : int32_t {
   NOT_FINISHED = -1, FINISH_STOP = 0, FINISH_LENGTH = 1, FINISH_ABORT = 2,
@@ -162,6 +175,12 @@ struct Sequence {
   int32_t pen_synced = 0;
   bool pen_fresh = false;
   bool penalised() const { return !embed && (presence_penalty != 0.f || frequency_penalty != 0.f); }
+  // logit_bias (unique token ids, non-zero values, at most LOGIT_BIAS_MAX) and min_p with the
+  // float32(ln min_p) the host computed at submit: fixed for the life of the request, no
+  // device state, so every sampling row of the sequence simply carries them
+  std::vector<std::pair<int32_t, float>> logit_bias;
+  float min_p = 0.f, ln_min_p = 0.f;
+  bool shaped() const { return !embed && (!logit_bias.empty() || min_p > 0.f); }
   bool ignore_eos = false;
   std::vector<int32_t> stop_ids;
   int64_t arrival = 0;
@@ -196,7 +215,9 @@ class Scheduler {
                    int64_t seed, bool ignore_eos, std::vector<int32_t> stop_ids,
                    std::unique_ptr<Grammar> grammar, int32_t top_k = 0, float top_p = 1.0f,
                    bool embed = false, bool embed_last = false, int32_t logprobs = -1,
-                   float presence_penalty = 0.f, float frequency_penalty = 0.f);
+                   float presence_penalty = 0.f, float frequency_penalty = 0.f,
+                   std::vector<std::pair<int32_t, float>> logit_bias = {}, float min_p = 0.f,
+                   float ln_min_p = 0.f);
   bool abort(int64_t id);
   // Fill `buf` (layout()) for the next step. Returns the number of tokens in the
   // step (0 = nothing to run).

@@ -82,6 +82,9 @@ class LLMConfig(BaseModel):
     # OpenAI penalties over a reply's generated tokens, the request defaults (0 = off)
     presence_penalty: float = Field(default=0.0, ge=-2.0, le=2.0)
     frequency_penalty: float = Field(default=0.0, ge=-2.0, le=2.0)
+    # min_p truncation, the request default (0 = off): at temperature > 0 keep the tokens whose
+    # probability is at least min_p times the most likely one's
+    min_p: float = Field(default=0.0, ge=0.0, le=1.0)
     max_tokens: int = Field(default=2000, gt=0)
     function_calling_model: Optional[str] = None
     system_template: Optional[str] = None

@@ -37,7 +37,8 @@ from collections import deque
 import threading
 import time
 from dataclasses import dataclass, field
-from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple, Union
+from numbers import Integral
+from typing import Any, Callable, Dict, List, Mapping, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -45,6 +46,7 @@ import torch
 from pilottai_amd import ops
 from pilottai_amd.engine.tp_sampling import tp_topkp_threshold
 from pilottai_amd.models.llama import KVCache, LlamaModel, StepMeta, get_config
+from pilottai_amd.ops.reference import ln_min_p as ref_ln_min_p
 from pilottai_amd.parallel.comm import TPGroup
 from pilottai_amd.utils.tracing import trace_range
 
@@ -211,6 +213,9 @@ class _Request:
     logprobs: int = -1        # -1 off, 0 the chosen token only, 1..20 with that many alternatives
     presence_penalty: float = 0.0   # OpenAI penalties over the generated tokens, each in [-2, 2]
     frequency_penalty: float = 0.0
+    logit_bias: tuple = ()          # ((token id, bias), ...): unique ids, non-zero values in [-100, 100]
+    min_p: float = 0.0              # 0 off; else in (0, 1]
+    ln_min_p: float = 0.0           # float32(ln min_p), computed once here for host and device
 
 
 class LLMEngine:
@@ -388,7 +393,8 @@ class LLMEngine:
         # one graph per (token bucket, top-k/top-p pass, embedding pooling); truncating variants
         # are captured on first use, so steps without truncation pay nothing for it. The variant
         # with the log-probability pass has the 4-tuple key (bucket, trunc, embed, True), a step
-        # with a penalised row the 5-tuple key (bucket, trunc, embed, lp, True).
+        # with a penalised row the 5-tuple key (bucket, trunc, embed, lp, True), a step with a
+        # logit_bias / min_p row the 6-tuple key (bucket, trunc, embed, lp, pen, True).
         self._graphs: Dict[tuple, "torch.cuda.CUDAGraph"] = {}
         self._tau = torch.empty(S, dtype=torch.float32, device=self.device)
         self._graph_pool = None
@@ -484,6 +490,12 @@ class LLMEngine:
         self._pair_start = sl("pair_start", ms)
         self._pair_n = sl("pair_n", ms)
         self._pair_tok = sl("pair_tok", L["pair_cap"])
+        self._bias_start = sl("bias_start", ms)
+        self._bias_n = sl("bias_n", ms)
+        self._minp = sl("minp", ms).view(torch.float32)
+        self._ln_minp = sl("ln_minp", ms).view(torch.float32)
+        self._bias_tok = sl("bias_tok", L["bias_cap"])
+        self._bias_val = sl("bias_val", L["bias_cap"]).view(torch.float32)
 
     def _sync_masks(self) -> bool:
         reg = self.grammar.reg
@@ -511,7 +523,7 @@ class LLMEngine:
                                                 self.device)
 
     def _forward_and_sample(self, bucket: int, s_b: int, ns: int, trunc: bool = False, embed: bool = False,
-                            lp: bool = False, pen: bool = False):
+                            lp: bool = False, pen: bool = False, shape: bool = False):
         meta = self._meta_for(bucket, s_b, ns)
         if self._async:  # pending tokens of rows that sampled in the previous step
             ops.patch_pending_ids(meta.input_ids[:bucket], self._sampled_dev)
@@ -523,6 +535,11 @@ class LLMEngine:
             ops.apply_penalties(logits, self._pen_state, self._pen_slot[:s_b],
                                 self._pen_reset[:s_b], self._pen_presence[:s_b], self._pen_frequency[:s_b],
                                 self._forced[:s_b], self._pair_start[:s_b], self._pair_n[:s_b], self._pair_tok)
+        if shape:
+            # logit_bias behind the penalties: the grammar mask, the thresholds, the sampler and
+            # the logprob pass all see the biased logits
+            ops.apply_logit_bias(logits, self._bias_start[:s_b], self._bias_n[:s_b], self._bias_tok,
+                                 self._bias_val, self._forced[:s_b])
         tau = None
         if trunc:
             # exact top-k / top-p threshold on the full vocabulary; under TP from all-reduced
@@ -536,6 +553,12 @@ class LLMEngine:
                                          self._temp[:s_b], self._top_k[:s_b], self._top_p[:s_b],
                                          self._mask_cls[:s_b], self._class_masks, self.tp, out=self._tau[:s_b],
                                          ws=self._tkp_ws)
+        if shape:
+            # min_p: raises the row's threshold to the larger of the two (the intersection of
+            # the kept sets); without a top-k / top-p pass it writes every row's tau
+            tau = ops.minp_threshold(logits, self._temp[:s_b], self._minp[:s_b], self._ln_minp[:s_b],
+                                     self._forced[:s_b], self._mask_cls[:s_b], self._class_masks,
+                                     tau=tau, out=self._tau[:s_b])
         if self.tp.size == 1:
             ops.sample(logits, self._temp[:s_b], self._mask_cls[:s_b], self._class_masks,
                        self._seeds[:s_b], self._offsets[:s_b], self._forced[:s_b],
@@ -559,27 +582,33 @@ class LLMEngine:
                                out=(o_lp[:s_b], o_ids[:s_b], o_lps[:s_b]), workspace=self._lp_ws)
 
     @staticmethod
-    def _graph_key(bucket: int, trunc: bool, embed: bool, lp: bool = False, pen: bool = False) -> tuple:
+    def _graph_key(bucket: int, trunc: bool, embed: bool, lp: bool = False, pen: bool = False,
+                   shape: bool = False) -> tuple:
+        if shape:
+            return (bucket, trunc, embed, lp, pen, True)
         if pen:
             return (bucket, trunc, embed, lp, True)
         return (bucket, trunc, embed, True) if lp else (bucket, trunc, embed)
 
     def _run(self, bucket: int, ns: int, trunc: bool, n_copy: int, embed: bool = False, lp: bool = False,
-             pen: bool = False):
-        """Replay the (bucket, trunc, embed[, logprobs[, penalties]]) graph — capturing it first if
-        needed — or run eagerly."""
+             pen: bool = False, shape: bool = False):
+        """Replay the (bucket, trunc, embed[, logprobs[, penalties[, shaping]]]) graph — capturing
+        it first if needed — or run eagerly."""
         if pen:
             self._ensure_pen_state()
         if not self.use_graphs:
-            self._forward_and_sample(bucket, self._seq_bucket(bucket), ns, trunc, embed, lp, pen)
+            self._forward_and_sample(bucket, self._seq_bucket(bucket), ns, trunc, embed, lp, pen, shape)
             return
-        key = self._graph_key(bucket, trunc, embed, lp, pen)
+        key = self._graph_key(bucket, trunc, embed, lp, pen, shape)
         g = self._graphs.get(key)
         if g is None:
+            if shape:  # the shaping regions lie behind the copied prefix: keep the whole buffer
+                n_copy = self.L["total"]
             saved = self._dev_meta[:n_copy].clone()
             pool = self._embed_pool.clone()
             samp = self._sampled_dev.clone()  # the previous step's tokens (pipelined mode)
-            self.capture_graphs([bucket], trunc=trunc, embed=embed, lp=lp, pen=pen)  # clobbers the device metadata
+            self.capture_graphs([bucket], trunc=trunc, embed=embed, lp=lp, pen=pen,
+                                shape=shape)  # clobbers the device metadata
             self.stats["graph_captures"] += 1  # a first-use capture inside serving (tens of ms)
             self._dev_meta[:n_copy].copy_(saved)
             self._embed_pool.copy_(pool)
@@ -587,6 +616,16 @@ class LLMEngine:
             g = self._graphs[key]
         g.replay()
         self.stats["graph_replays"] += 1
+
+    def _copy_shaping(self, hm: torch.Tensor, n_bias: int):
+        """Host -> device copy of the logit_bias / min_p regions of a step with a shaped row: the
+        per-row words and the `n_bias` bias tokens in one piece, the bias values in a second."""
+        L = self.L
+        a, b = L["bias_start"], L["bias_tok"] + n_bias
+        self._dev_meta[a:b].copy_(hm[a:b], non_blocking=self.on_gpu)
+        if n_bias:
+            a = L["bias_val"]
+            self._dev_meta[a:a + n_bias].copy_(hm[a:a + n_bias], non_blocking=self.on_gpu)
 
     def _seq_bucket(self, bucket: int) -> int:
         return min(bucket, self.cfg.max_num_seqs)
@@ -598,6 +637,7 @@ class LLMEngine:
         d[L["slots"]:L["slots"] + L["max_tokens"]] = -1
         d[L["embed_rows"]:L["embed_rows"] + L["max_tokens"]] = L["max_seqs"]
         d[L["pen_slot"]:L["pen_slot"] + L["max_seqs"]] = -1  # the penalty pass touches nothing
+        # bias_n = 0 and min_p = 0 (the zeros above): the logit_bias / min_p passes touch nothing
         self._dev_meta.copy_(d.to(self.device))
 
     def capture_embed_graphs(self):
@@ -608,9 +648,10 @@ class LLMEngine:
         self.capture_graphs(embed=True)
 
     def capture_graphs(self, buckets: Optional[Sequence[int]] = None, trunc: bool = False, embed: bool = False,
-                       lp: bool = False, pen: bool = False):
+                       lp: bool = False, pen: bool = False, shape: bool = False):
         """Capture one hipGraph per token bucket (shared memory pool); the top-k/top-p,
-        embedding-pooling, log-probability and penalty variants are captured on first use."""
+        embedding-pooling, log-probability, penalty and logit_bias / min_p (`shape`) variants
+        are captured on first use, or up front by a call with the flag set."""
         if not self.use_graphs:
             return
         if pen:
@@ -620,7 +661,7 @@ class LLMEngine:
             self._graph_pool = torch.cuda.graph_pool_handle()
         t0 = time.time()
         for b in sorted(buckets or self.buckets, reverse=True):
-            key = self._graph_key(b, trunc, embed, lp, pen)
+            key = self._graph_key(b, trunc, embed, lp, pen, shape)
             if key in self._graphs:
                 continue
             s_b = self._seq_bucket(b)
@@ -628,11 +669,11 @@ class LLMEngine:
             st.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(st):
                 for _ in range(2):
-                    self._forward_and_sample(b, s_b, 0, trunc, embed, lp, pen)
+                    self._forward_and_sample(b, s_b, 0, trunc, embed, lp, pen, shape)
             torch.cuda.current_stream().wait_stream(st)
             g = torch.cuda.CUDAGraph(keep_graph=True) if self.cfg.keep_graphs else torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, pool=self._graph_pool):
-                self._forward_and_sample(b, s_b, 0, trunc, embed, lp, pen)
+                self._forward_and_sample(b, s_b, 0, trunc, embed, lp, pen, shape)
             if self.cfg.keep_graphs:
                 g.instantiate()
             self._graphs[key] = g
@@ -648,12 +689,41 @@ class LLMEngine:
             self._next_id += 1
             return rid
 
+    @staticmethod
+    def check_logit_bias(logit_bias, vocab_size: Optional[int] = None) -> tuple:
+        """Validate a `logit_bias` mapping (None = empty) and return it as ((id, bias), ...) sorted
+        by id with the zero entries dropped; ValueError for anything outside the rules."""
+        if logit_bias is None:
+            return ()
+        if not isinstance(logit_bias, Mapping):
+            raise ValueError("logit_bias must be a mapping of token id to bias")
+        if len(logit_bias) > ops.LOGIT_BIAS_MAX:
+            raise ValueError(f"logit_bias takes at most {ops.LOGIT_BIAS_MAX} entries, not {len(logit_bias)}")
+        out = {}
+        for t, b in logit_bias.items():
+            if isinstance(t, bool) or not isinstance(t, Integral) or t < 0 or (vocab_size is not None and t >= vocab_size):
+                raise ValueError(f"logit_bias token id {t!r} is not an integer in [0, vocab_size)")
+            if isinstance(b, bool) or not isinstance(b, (int, float)) or not -100.0 <= b <= 100.0:  # NaN fails too
+                raise ValueError(f"logit_bias[{t}] must be a finite number in [-100, 100], not {b!r}")
+            if b != 0:
+                out[int(t)] = float(b)
+        return tuple(sorted(out.items()))
+
+    @staticmethod
+    def check_min_p(min_p) -> float:
+        """Validate `min_p` (None = 0 = off): a finite number in [0, 1], else ValueError."""
+        v = 0.0 if min_p is None else min_p
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 <= v <= 1.0:  # NaN fails too
+            raise ValueError(f"min_p must be a number in [0, 1], not {v!r}")
+        return float(v)
+
     def submit(self, prompt_ids: Sequence[int], callback: Callable[[GenerationOutput], None], *,
                temperature: float = 0.7, max_tokens: int = 256, seed: Optional[int] = None,
                ignore_eos: bool = False, stop_ids: Sequence[int] = (), grammar: Optional[list] = None,
                request_id: Optional[int] = None, top_k: int = 0, top_p: float = 1.0,
                embed: Union[bool, str] = False, logprobs: int = -1, presence_penalty: float = 0.0,
-               frequency_penalty: float = 0.0) -> int:
+               frequency_penalty: float = 0.0, logit_bias: Optional[Mapping[int, float]] = None,
+               min_p: float = 0.0) -> int:
         """Thread-safe; `callback` runs on the engine thread when the request finishes.
 
         top_k > 0 / top_p < 1 truncate the (grammar-masked) distribution before
@@ -674,7 +744,18 @@ class LLMEngine:
         logit[t] -= a * [c_t > 0] + b * c_t with c_t the occurrences of t among the request's
         generated tokens so far (sampled and grammar-forced; the prompt is not counted). Both 0:
         the request is exactly what it is without them. Not for embedding requests, not on a
-        TP > 1 engine, not with async_steps."""
+        TP > 1 engine, not with async_steps.
+
+        logit_bias {token id: b}, at most 300 entries, ids in [0, vocab_size), b finite in
+        [-100, 100] (zero entries are dropped): at every sampling step, behind the penalties and
+        before everything else, logit[t] <- bf16(float(logit[t]) + b). The grammar mask still
+        applies, so a biased token the grammar does not allow stays impossible; logprobs are those
+        of the biased distribution. min_p p in [0, 1] (0 off): at temperature T > 0 the row keeps
+        the allowed tokens with logit >= m + T * float32(ln p), m the largest allowed logit (i.e.
+        probability >= p * the largest), intersected with top_k / top_p; greedy rows and logprobs
+        ignore it. Both are stateless on the device: they work with async_steps and across
+        preemption. An empty bias with min_p = 0 is exactly the request without them. Not for
+        embedding requests, not on a TP > 1 engine."""
         if self._err is not None:
             raise RuntimeError(f"engine failed: {self._err!r}")
         logprobs = -1 if logprobs is None else int(logprobs)
@@ -699,13 +780,20 @@ class LLMEngine:
                 raise ValueError("penalties are not supported on an async_steps engine")
             if self._pen_slots < 1:
                 raise ValueError("penalties need EngineConfig.penalty_slots >= 1")
+        bias = self.check_logit_bias(logit_bias, self.model_cfg.vocab_size)
+        min_p = self.check_min_p(min_p)
+        if bias or min_p > 0.0:
+            if embed:
+                raise ValueError("logit_bias / min_p are not available on embedding requests")
+            if self.tp.size > 1:
+                raise ValueError("logit_bias / min_p are not supported on a tensor-parallel (TP > 1) engine")
         rid = request_id if request_id is not None else self.new_request_id()
         if seed is None:
             seed = (self.cfg.seed * 0x9E3779B1 + rid * 0x85EBCA77) & 0x7FFFFFFFFFFFFFFF
         req = _Request(rid, list(prompt_ids), float(temperature), int(max_tokens), int(seed),
                        bool(ignore_eos), list(stop_ids), grammar, callback, self._rt.now(),
                        int(top_k or 0), float(1.0 if top_p is None else top_p), bool(embed), embed == "last",
-                       logprobs, pens[0], pens[1])
+                       logprobs, pens[0], pens[1], bias, min_p, ref_ln_min_p(min_p))
         self._inbox.put(req)
         self._wake.set()
         return rid
@@ -937,7 +1025,8 @@ class LLMEngine:
             self._reqs[req.rid] = req
             self.sched.add_request(req.rid, req.prompt_ids, req.temperature, req.max_tokens, req.seed,
                                    req.ignore_eos, req.stop_ids, req.grammar, req.top_k, req.top_p, req.embed,
-                                   req.embed_last, req.logprobs, req.presence_penalty, req.frequency_penalty)
+                                   req.embed_last, req.logprobs, req.presence_penalty, req.frequency_penalty,
+                                   list(req.logit_bias), req.min_p, req.ln_min_p)
             self.stats["requests"] += 1
         while True:
             try:
@@ -995,9 +1084,10 @@ class LLMEngine:
             if self.sched.num_running == 0 and self.sched.num_waiting > 0:
                 raise RuntimeError("KV cache too small for the head request")
             return False
-        c = self._host_np[L["counts"]:L["counts"] + 11]
+        c = self._host_np[L["counts"]:L["counts"] + 12]
         ns, nsamp, trunc, embed, lp = int(c[1]), int(c[2]), int(c[6]) > 0, int(c[7]) > 0, int(c[8]) > 0
         pen = int(c[9]) > 0
+        shape = int(c[11])  # 0, or 1 + the bias words of the step's logit_bias / min_p rows
         bucket = next(b for b in self.buckets if b >= T)
         s_b = self._seq_bucket(bucket)
         masks_changed = self._sync_masks()
@@ -1009,13 +1099,15 @@ class LLMEngine:
             self._embed_pool[torch.tensor(resets, dtype=torch.long, device=self.device)] = 0.0
         if self.on_gpu:
             self._dev_meta[:n_copy].copy_(self._host_meta[:n_copy], non_blocking=True)
+            if shape:
+                self._copy_shaping(self._host_meta, shape - 1)
         if self.tp.size > 1:
             self._tp_send(_OP_STEP, T, ns, nsamp, bucket, int(masks_changed), n_copy, int(trunc), int(embed))
             if masks_changed:
                 self.tp.broadcast(self._class_masks)
             self.tp.broadcast(self._dev_meta[:n_copy])
         with torch.inference_mode(), trace_range("engine.forward"):
-            self._run(bucket, ns, trunc, n_copy, embed, lp, pen)
+            self._run(bucket, ns, trunc, n_copy, embed, lp, pen, shape > 0)
         if self._step_listeners:
             self._notify_launch(T)
         if nsamp:
@@ -1088,8 +1180,9 @@ class LLMEngine:
             if not self._inflight and self.sched.num_running == 0 and self.sched.num_waiting > 0:
                 raise RuntimeError("KV cache too small for the head request")
             return False
-        c = hm.numpy()[L["counts"]:L["counts"] + 9]
+        c = hm.numpy()[L["counts"]:L["counts"] + 12]
         ns, nsamp, trunc, embed, lp = int(c[1]), int(c[2]), int(c[6]) > 0, int(c[7]) > 0, int(c[8]) > 0
+        shape = int(c[11])  # 0, or 1 + the bias words of the step's logit_bias / min_p rows
         bucket = next(b for b in self.buckets if b >= T)
         self._sync_masks()
         n_copy = L["embed_rows"] + bucket if embed else L["block_table"] + ns * L["max_blocks"]
@@ -1097,8 +1190,10 @@ class LLMEngine:
         if resets:
             self._embed_pool[torch.tensor(resets, dtype=torch.long, device=self.device)] = 0.0
         self._dev_meta[:n_copy].copy_(hm[:n_copy], non_blocking=self.on_gpu)
+        if shape:
+            self._copy_shaping(hm, shape - 1)
         with torch.inference_mode(), trace_range("engine.forward"):
-            self._run(bucket, ns, trunc, n_copy, embed, lp)
+            self._run(bucket, ns, trunc, n_copy, embed, lp, shape=shape > 0)
         if self._step_listeners:
             self._notify_launch(T)
         if nsamp:

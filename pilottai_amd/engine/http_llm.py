@@ -14,7 +14,9 @@ OpenAI-compatible server, pass `schema_mode="json_object"` to send
 `{"type": "json_object"}` instead. `response_format["logprobs"] = n` (0..20) is sent as
 `logprobs: true, top_logprobs: n`; the reply's `logprobs.content` comes back as `r["logprobs"]`.
 `response_format["presence_penalty"]` / `["frequency_penalty"]` (or the `LLMConfig` defaults of
-the same names) are sent under their OpenAI names when non-zero.
+the same names) are sent under their OpenAI names when non-zero. `response_format["logit_bias"]`
+({token id: bias}) is sent in the OpenAI wire form (keys as strings), `response_format["min_p"]`
+(default `LLMConfig.min_p`) as `min_p` when non-zero.
 
     LLMConfig(provider="openai", base_url="http://10.0.0.5:8000/v1", api_key=...)
 """
@@ -29,6 +31,7 @@ class OpenAICompatLLM(BaseLLM):
     provider = "openai"
     supports_logprobs = True
     supports_penalties = True
+    supports_logit_shaping = True
 
     def __init__(self, config: Any = None, base_url: Optional[str] = None, timeout_s: float = 600.0,
                  schema_mode: str = "pilottai"):
@@ -69,6 +72,11 @@ class OpenAICompatLLM(BaseLLM):
             v = rf.get(k, getattr(self, k))
             if v:
                 body[k] = float(v)
+        if rf.get("logit_bias"):
+            body["logit_bias"] = {str(int(t)): float(b) for t, b in rf["logit_bias"].items()}
+        mp = rf.get("min_p", self.min_p)
+        if mp:
+            body["min_p"] = float(mp)
         if tools:
             body["tools"] = self._format_tools(tools)
         elif rf.get("schema") is not None:

@@ -112,6 +112,8 @@ class BaseLLM:
     supports_logprobs = False  # response_format["logprobs"] is honoured and r["logprobs"] returned
     # response_format["presence_penalty"] / ["frequency_penalty"] are honoured
     supports_penalties = False
+    # response_format["logit_bias"] ({token id: bias}) / ["min_p"] are honoured
+    supports_logit_shaping = False
 
     def __init__(self, config: Any = None):
         self.config = config
@@ -122,6 +124,8 @@ class BaseLLM:
         # request defaults of the OpenAI penalties over the generated tokens (0 = off)
         self.presence_penalty = float(_cfg_get(config, "presence_penalty", 0.0) or 0.0)
         self.frequency_penalty = float(_cfg_get(config, "frequency_penalty", 0.0) or 0.0)
+        # request default of min_p truncation (0 = off); a logit_bias has no config default
+        self.min_p = float(_cfg_get(config, "min_p", 0.0) or 0.0)
         self.max_tokens = int(_cfg_get(config, "max_tokens", 2000))
         self.retry_attempts = max(1, int(_cfg_get(config, "retry_attempts", 3)))
         self.retry_delay = float(_cfg_get(config, "retry_delay", 1.0))
@@ -195,6 +199,7 @@ class LocalLLM(BaseLLM):
     provider = "local"
     supports_logprobs = True
     supports_penalties = True
+    supports_logit_shaping = True
     prefix_cache_layout = True  # agents put the shared task text first (core/agent.py)
 
     def __init__(self, config: Any = None, engine=None):
@@ -240,7 +245,8 @@ class LocalLLM(BaseLLM):
                                  top_p=float(rf.get("top_p", self.top_p)),
                                  logprobs=-1 if rf.get("logprobs") is None else int(rf["logprobs"]),
                                  presence_penalty=rf.get("presence_penalty", self.presence_penalty),
-                                 frequency_penalty=rf.get("frequency_penalty", self.frequency_penalty))
+                                 frequency_penalty=rf.get("frequency_penalty", self.frequency_penalty),
+                                 logit_bias=rf.get("logit_bias"), min_p=rf.get("min_p", self.min_p))
         try:
             out = await fut
         except asyncio.CancelledError:

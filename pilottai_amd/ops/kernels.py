@@ -272,6 +272,48 @@ def apply_penalties(logits, state, pen_slot, pen_reset, presence, frequency, for
     return logits
 
 
+LOGIT_BIAS_MAX = 300        # entries of one request's logit_bias (the OpenAI API's bound)
+LOGIT_BIAS_LAUNCHES = 1     # kernels apply_logit_bias() launches on the GPU
+MINP_THRESHOLD_LAUNCHES = 1  # kernels minp_threshold() launches on the GPU
+
+
+def apply_logit_bias(logits, bias_start, bias_n, bias_tok, bias_val, forced):
+    """logit_bias, in place on `logits` [rows, V] bf16 (csrc/ops/logit_shaping.hip).
+
+    Row r with bias_n[r] > 0 and forced[r] < 0: for i in [bias_start[r], bias_start[r] +
+    bias_n[r]), logit[bias_tok[i]] <- bf16(float(logit[bias_tok[i]]) + bias_val[i]) -- one fp32
+    add, one round-to-nearest-even conversion. Token ids outside [0, V) are skipped, a list that
+    leaves bias_tok is not applied, nothing else in the row is touched. A row's ids are unique."""
+    if _on_gpu(logits):
+        require_native().apply_logit_bias(logits, bias_start, bias_n, bias_tok, bias_val, forced)
+        return logits
+    ref.apply_logit_bias(logits, bias_start, bias_n, bias_tok, bias_val, forced)
+    return logits
+
+
+def minp_threshold(logits, temperature, min_p, ln_min_p, forced, mask_class, class_masks,
+                   tau: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """min_p truncation as a per-row logit threshold (csrc/ops/logit_shaping.hip).
+
+    Row r with min_p[r] > 0, temperature[r] > 0 and forced[r] < 0: m = the largest logit among
+    the tokens its mask class allows, tau_mp = fadd_rn(m, fmul_rn(temperature[r], ln_min_p[r]))
+    (ln_min_p = float32(ln p), computed by the caller). `tau` = the step's top-k / top-p
+    thresholds: updated in place to max(tau, tau_mp), other rows keep their value. Without
+    `tau` the result goes to `out` (or a new tensor), other rows get -inf = no truncation, as
+    do rows whose mask allows nothing."""
+    rows = logits.shape[0]
+    has_tau = tau is not None
+    if not has_tau:
+        tau = out if out is not None else torch.empty(rows, dtype=torch.float32, device=logits.device)
+    if _on_gpu(logits):
+        require_native().minp_threshold(tau, has_tau, logits, temperature, min_p, ln_min_p, forced,
+                                        mask_class, class_masks)
+        return tau
+    tau[:rows].copy_(ref.minp_threshold(logits, temperature, min_p, ln_min_p, forced, mask_class, class_masks,
+                                        tau[:rows] if has_tau else None))
+    return tau
+
+
 COSINE_MAX_Q = 64  # queries per index pass (LDS-resident query tiles)
 
 

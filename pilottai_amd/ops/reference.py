@@ -317,6 +317,58 @@ def apply_penalties(logits: torch.Tensor, state, pen_slot, pen_reset, presence, 
     return logits
 
 
+def apply_logit_bias(logits: torch.Tensor, bias_start, bias_n, bias_tok, bias_val, forced):
+    """logit_bias in place on `logits` [rows, V] (see ops.apply_logit_bias): one fp32 add per
+    listed token, one conversion back to the logits' dtype."""
+    rows, V = logits.shape
+    for r in range(rows):
+        n, a0 = int(bias_n[r]), int(bias_start[r])
+        if n <= 0 or int(forced[r]) >= 0 or a0 < 0 or a0 + n > bias_tok.numel():
+            continue
+        idx = bias_tok[a0:a0 + n].long()
+        val = bias_val[a0:a0 + n].float()
+        ok = (idx >= 0) & (idx < V)
+        idx, val = idx[ok], val[ok]
+        logits[r, idx] = (logits[r, idx].float() + val).to(logits.dtype)
+    return logits
+
+
+def ln_min_p(p: float) -> float:
+    """float32(ln p), the form in which a request's min_p travels to the device: computed in
+    double precision, rounded once. 0.0 for p outside (0, 1] (min_p off)."""
+    p = float(p)
+    return float(np.float32(np.log(np.float64(p)))) if 0.0 < p <= 1.0 else 0.0
+
+
+def minp_threshold(logits: torch.Tensor, temperature, min_p, ln_min_p, forced, mask_class, class_masks,
+                   tau=None):
+    """min_p as a logit threshold per row (see ops.minp_threshold): tau_mp = m + T * L with m
+    the largest allowed logit, the product and the sum each rounded to float32. Rows with
+    min_p <= 0, T <= 0, a forced token or a mask that allows nothing keep `tau` (-inf without
+    it); the others get max(tau, tau_mp). Returns fp32 [rows]."""
+    rows, V = logits.shape
+    out = (tau.detach().cpu().float().clone() if tau is not None
+           else torch.full((rows,), float("-inf"), dtype=torch.float32))
+    lg = logits.float().cpu().numpy()  # bf16 -> fp32 is exact
+    cm = class_masks.cpu().numpy().view(np.uint32) if class_masks is not None else None
+    idx = np.arange(V)
+    for r in range(rows):
+        p, T = float(min_p[r]), float(temperature[r])
+        mc = int(mask_class[r])
+        if not p > 0.0 or not T > 0.0 or int(forced[r]) >= 0 or (cm is not None and mc >= cm.shape[0]):
+            continue
+        vals = lg[r]
+        if mc >= 0 and cm is not None:
+            vals = vals[((cm[mc][idx >> 5] >> (idx & 31).astype(np.uint32)) & 1).astype(bool)]
+        if vals.size == 0:
+            continue
+        m = np.float32(vals.max())
+        with np.errstate(invalid="ignore", over="ignore"):
+            t_mp = np.float32(m + np.float32(np.float32(T) * np.float32(float(ln_min_p[r]))))
+        out[r] = max(float(out[r]), float(t_mp))
+    return out
+
+
 # ---------------------------------------------------------------------------
 # semantic index
 # ---------------------------------------------------------------------------

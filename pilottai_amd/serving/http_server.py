@@ -29,7 +29,15 @@ grammar-forced token has 0.0). Each entry also carries `token_id`; -inf is sent 
 `presence_penalty` / `frequency_penalty` (numbers in [-2, 2], OpenAI semantics over the
 GENERATED tokens: logit[t] -= presence * [c_t > 0] + frequency * c_t) are applied by the engine
 before the grammar mask, top-k / top-p, the sampler and the logprob pass; 0 or absent means
-nothing. `logit_bias`, a multiplicative `repetition_penalty` and `n > 1` are not supported.
+nothing. A multiplicative `repetition_penalty` and `n > 1` are not supported.
+
+`logit_bias` (the OpenAI wire form: an object of at most 300 entries whose keys are token ids
+as strings and whose values are numbers in [-100, 100]) is added to those logits at every
+sampling step, behind the penalties and before the grammar mask -- a token the reply's grammar
+does not allow stays impossible, so -100 bans an enum value or a tool name and the reply still
+parses. `min_p` (a number in [0, 1], the vLLM extension) keeps, at temperature > 0, the allowed
+tokens whose probability is at least min_p times the most likely one's, intersected with
+top_k / top_p. Malformed values answer 400.
 
 Every request becomes one `LocalLLM` call, i.e. one sequence in the engine's continuous
 batch. Concurrent HTTP clients share the engine's steps exactly like in-process agents.
@@ -132,6 +140,48 @@ def _penalties(body: Dict[str, Any]) -> Dict[str, float]:
     return out
 
 
+LOGIT_BIAS_MAX = 300  # entries of one request's logit_bias (ops.LOGIT_BIAS_MAX)
+
+
+def _shaping(body: Dict[str, Any], vocab_size: Optional[int] = None) -> Dict[str, Any]:
+    """The request's `logit_bias` ({token id: bias}, zero entries dropped) and non-zero `min_p`."""
+    out: Dict[str, Any] = {}
+    lb = body.get("logit_bias")
+    if lb is not None:
+        if not isinstance(lb, dict):
+            raise ValueError("logit_bias must be an object of token id -> bias")
+        if len(lb) > LOGIT_BIAS_MAX:
+            raise ValueError(f"logit_bias takes at most {LOGIT_BIAS_MAX} entries")
+        bias: Dict[int, float] = {}
+        for k, v in lb.items():
+            try:
+                if isinstance(k, bool) or not isinstance(k, (str, int)):
+                    raise ValueError
+                t = int(k.strip(), 10) if isinstance(k, str) else k
+            except ValueError:
+                raise ValueError(f"logit_bias key {k!r} is not a token id") from None
+            if t < 0 or (vocab_size is not None and t >= vocab_size):
+                raise ValueError(f"logit_bias token id {t} is outside the vocabulary")
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not -100.0 <= v <= 100.0:  # NaN fails too
+                raise ValueError(f"logit_bias[{t}] must be a number between -100 and 100")
+            if t in bias:
+                raise ValueError(f"logit_bias names token id {t} twice")
+            if v != 0:
+                bias[t] = float(v)
+            else:
+                bias.setdefault(t, 0.0)
+        bias = {t: v for t, v in bias.items() if v != 0}
+        if bias:
+            out["logit_bias"] = bias
+    mp = body.get("min_p")
+    if mp is not None:
+        if isinstance(mp, bool) or not isinstance(mp, (int, float)) or not 0.0 <= mp <= 1.0:  # NaN fails too
+            raise ValueError("min_p must be a number between 0 and 1")
+        if mp != 0:
+            out["min_p"] = float(mp)
+    return out
+
+
 def _logprobs(body: Dict[str, Any]) -> int:
     """The number of alternatives asked for (-1: no logprobs), from `logprobs` / `top_logprobs`."""
     want, top = body.get("logprobs"), body.get("top_logprobs")
@@ -206,8 +256,15 @@ def create_app(llm, model_name: Optional[str] = None, engine=None) -> FastAPI:
             tools = _tools(body)
             n_lp = _logprobs(body)
             pens = _penalties(body)
+            eng = engine or getattr(llm, "engine", None)
+            shaping = _shaping(body, getattr(getattr(eng, "model_cfg", None), "vocab_size", None))
         except (KeyError, ValueError) as e:
             raise HTTPException(400, str(e))
+        if shaping:
+            if not getattr(llm, "supports_logit_shaping", False):
+                raise HTTPException(400, f"the {getattr(llm, 'provider', 'configured')} backend cannot apply "
+                                         "logit_bias / min_p")
+            rf = dict(rf or {}, **shaping)
         if pens:
             if not getattr(llm, "supports_penalties", False):
                 raise HTTPException(400, f"the {getattr(llm, 'provider', 'configured')} backend cannot apply "
