@@ -35,6 +35,11 @@ int pa_apply_penalties(void* logits, int rows, int V, int ld, int* counts, int* 
                        int slots, int cap, const int* pen_slot, const int* pen_reset, const float* presence,
                        const float* frequency, const int* forced, const int* pair_start, const int* pair_n,
                        const int* pair_tok, int pair_len, hipStream_t st);
+int pa_apply_repetition_penalty(void* logits, int rows, int V, int ld, uint32_t* seen, int words, int* list,
+                                int* n_list, int slots, int cap, const int* rep_slot, const int* rep_reset,
+                                const float* rep_r, const float* rep_inv_r, const int* forced,
+                                const int* rep_start, const int* rep_n, const int* rep_tok, int tok_len,
+                                hipStream_t st);
 int pa_apply_logit_bias(void* logits, int rows, int V, int ld, const int* bias_start, const int* bias_n,
                         const int* bias_tok, const float* bias_val, int bias_len, const int* forced,
                         hipStream_t st);
@@ -758,6 +763,52 @@ void apply_penalties(at::Tensor logits, at::Tensor counts, at::Tensor distinct, 
            "apply_penalties");
 }
 
+// Repetition penalty on the logits of the sampling rows that carry one (repetition.hip): seen
+// [slots, ceil(V / 32)] membership bits, seen_list [slots, cap], n_seen [slots] are the per-slot
+// device state.
+void apply_repetition_penalty(at::Tensor logits, at::Tensor seen, at::Tensor seen_list, at::Tensor n_seen,
+                              at::Tensor rep_slot, at::Tensor rep_reset, at::Tensor rep_r, at::Tensor rep_inv_r,
+                              at::Tensor forced, at::Tensor rep_start, at::Tensor rep_n, at::Tensor rep_tok) {
+  check_gpu(seen, "seen"); check_gpu(seen_list, "seen_list"); check_gpu(n_seen, "n_seen");
+  check_gpu(rep_slot, "rep_slot"); check_gpu(rep_reset, "rep_reset"); check_gpu(rep_r, "rep_r");
+  check_gpu(rep_inv_r, "rep_inv_r"); check_gpu(forced, "forced"); check_gpu(rep_start, "rep_start");
+  check_gpu(rep_n, "rep_n"); check_gpu(rep_tok, "rep_tok");
+  check_dtype(seen, at::kInt, "seen"); check_dtype(seen_list, at::kInt, "seen_list");
+  check_dtype(n_seen, at::kInt, "n_seen"); check_dtype(rep_slot, at::kInt, "rep_slot");
+  check_dtype(rep_reset, at::kInt, "rep_reset"); check_dtype(rep_r, at::kFloat, "rep_r");
+  check_dtype(rep_inv_r, at::kFloat, "rep_inv_r"); check_dtype(forced, at::kInt, "forced");
+  check_dtype(rep_start, at::kInt, "rep_start"); check_dtype(rep_n, at::kInt, "rep_n");
+  check_dtype(rep_tok, at::kInt, "rep_tok");
+  TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.scalar_type() == at::kBFloat16 &&
+                  (logits.size(1) == 1 || logits.stride(1) == 1),
+              "logits: [rows, V] bf16 GPU tensor with unit inner stride");
+  const int64_t rows = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(V > 0 && V < (int64_t(1) << 31), "logits: vocabulary out of range");
+  TORCH_CHECK(seen.dim() == 2 && seen.is_contiguous() && seen.size(1) == (V + 31) / 32,
+              "seen must be [slots, ceil(V / 32)]");
+  const int64_t slots = seen.size(0);
+  TORCH_CHECK(seen_list.dim() == 2 && seen_list.is_contiguous() && seen_list.size(0) == slots &&
+                  seen_list.size(1) >= 1 && seen_list.size(1) < (int64_t(1) << 31),
+              "seen_list must be [slots, cap]");
+  TORCH_CHECK(n_seen.numel() == slots && n_seen.is_contiguous(), "n_seen must be [slots]");
+  TORCH_CHECK(slots >= 1 && slots < (int64_t(1) << 31), "repetition state: slots out of range");
+  TORCH_CHECK(rep_slot.numel() >= rows && rep_reset.numel() >= rows && rep_r.numel() >= rows &&
+                  rep_inv_r.numel() >= rows && forced.numel() >= rows && rep_start.numel() >= rows &&
+                  rep_n.numel() >= rows,
+              "per-row repetition parameter tensors too short");
+  const int64_t ld = rows > 1 ? logits.stride(0) : V;  // a one-row view's stride is arbitrary
+  TORCH_CHECK(ld >= V && rows * ld < (int64_t(1) << 40) && rep_tok.numel() < (int64_t(1) << 31),
+              "logits row stride / token list out of range");
+  check_rc(pa_apply_repetition_penalty(
+               logits.data_ptr(), (int)rows, (int)V, (int)ld, reinterpret_cast<uint32_t*>(seen.data_ptr<int>()),
+               (int)seen.size(1), seen_list.data_ptr<int>(), n_seen.data_ptr<int>(), (int)slots,
+               (int)seen_list.size(1), rep_slot.data_ptr<int>(), rep_reset.data_ptr<int>(),
+               rep_r.data_ptr<float>(), rep_inv_r.data_ptr<float>(), forced.data_ptr<int>(),
+               rep_start.data_ptr<int>(), rep_n.data_ptr<int>(), rep_tok.data_ptr<int>(), (int)rep_tok.numel(),
+               cur_stream()),
+           "apply_repetition_penalty");
+}
+
 // logit_bias on the logits of the sampling rows (logit_shaping.hip): row r adds bias_val[i] to
 // logit[bias_tok[i]] for i in [bias_start[r], bias_start[r] + bias_n[r]).
 void apply_logit_bias(at::Tensor logits, at::Tensor bias_start, at::Tensor bias_n, at::Tensor bias_tok,
@@ -1162,6 +1213,9 @@ PYBIND11_MODULE(_C, m) {
   m.def("apply_penalties", &apply_penalties, py::arg("logits"), py::arg("counts"), py::arg("distinct"),
         py::arg("n_distinct"), py::arg("pen_slot"), py::arg("pen_reset"), py::arg("presence"),
         py::arg("frequency"), py::arg("forced"), py::arg("pair_start"), py::arg("pair_n"), py::arg("pair_tok"));
+  m.def("apply_repetition_penalty", &apply_repetition_penalty, py::arg("logits"), py::arg("seen"),
+        py::arg("seen_list"), py::arg("n_seen"), py::arg("rep_slot"), py::arg("rep_reset"), py::arg("rep_r"),
+        py::arg("rep_inv_r"), py::arg("forced"), py::arg("rep_start"), py::arg("rep_n"), py::arg("rep_tok"));
   m.def("apply_logit_bias", &apply_logit_bias, py::arg("logits"), py::arg("bias_start"), py::arg("bias_n"),
         py::arg("bias_tok"), py::arg("bias_val"), py::arg("forced"));
   m.def("minp_threshold", &minp_threshold, py::arg("tau"), py::arg("has_tau"), py::arg("logits"),

@@ -203,6 +203,9 @@ PYBIND11_MODULE(_runtime, m) {
         d["pair_tok"] = L.pair_tok; d["pair_cap"] = L.pair_cap;
         d["bias_start"] = L.bias_start; d["bias_n"] = L.bias_n; d["minp"] = L.minp; d["ln_minp"] = L.ln_minp;
         d["bias_tok"] = L.bias_tok; d["bias_val"] = L.bias_val; d["bias_cap"] = L.bias_cap;
+        d["rep_slot"] = L.rep_slot; d["rep_reset"] = L.rep_reset; d["rep_r"] = L.rep_r;
+        d["rep_inv_r"] = L.rep_inv_r; d["rep_start"] = L.rep_start; d["rep_n"] = L.rep_n;
+        d["rep_tok"] = L.rep_tok; d["rep_cap"] = L.rep_cap; d["rep_total"] = L.rep_total;
         d["total"] = L.total;
         return d;
       })
@@ -212,10 +215,11 @@ PYBIND11_MODULE(_runtime, m) {
               const std::vector<int32_t>& stop_ids, const py::object& grammar, int32_t top_k,
               float top_p, bool embed, bool embed_last, int32_t logprobs, float presence_penalty,
               float frequency_penalty, const std::vector<std::pair<int32_t, float>>& logit_bias,
-              float min_p, float ln_min_p) {
+              float min_p, float ln_min_p, float repetition_penalty, float inv_repetition_penalty) {
              s.add_request(id, prompt, temperature, max_tokens, seed, ignore_eos, stop_ids,
                            make_grammar(grammar), top_k, top_p, embed, embed_last, logprobs,
-                           presence_penalty, frequency_penalty, logit_bias, min_p, ln_min_p);
+                           presence_penalty, frequency_penalty, logit_bias, min_p, ln_min_p,
+                           repetition_penalty, inv_repetition_penalty);
            },
            py::arg("id"), py::arg("prompt"), py::arg("temperature"), py::arg("max_tokens"),
            py::arg("seed"), py::arg("ignore_eos"), py::arg("stop_ids"), py::arg("grammar"),
@@ -223,11 +227,14 @@ PYBIND11_MODULE(_runtime, m) {
            py::arg("embed_last") = false, py::arg("logprobs") = -1, py::arg("presence_penalty") = 0.0f,
            py::arg("frequency_penalty") = 0.0f,
            py::arg("logit_bias") = std::vector<std::pair<int32_t, float>>{}, py::arg("min_p") = 0.0f,
-           py::arg("ln_min_p") = 0.0f)
-      .def("schedule", [](Scheduler& s, uintptr_t buf) {
+           py::arg("ln_min_p") = 0.0f, py::arg("repetition_penalty") = 1.0f,
+           py::arg("inv_repetition_penalty") = 0.0f)
+      // words: the buffer's size in 32-bit words (0 = not stated: steps of requests with a
+      // repetition penalty, which write behind layout()["total"], are then refused)
+      .def("schedule", [](Scheduler& s, uintptr_t buf, int32_t words) {
         py::gil_scoped_release nogil;
-        return s.schedule(reinterpret_cast<int32_t*>(buf));
-      })
+        return s.schedule(reinterpret_cast<int32_t*>(buf), words);
+      }, py::arg("buf"), py::arg("words") = 0)
       // logprobs: address of the step's LogprobRecord array (41 32-bit words per sampling row:
       // logprob, 20 ids, 20 logprobs), 0 = the step computed none
       .def("commit", [](Scheduler& s, uintptr_t sampled, int32_t n, uintptr_t logprobs) {

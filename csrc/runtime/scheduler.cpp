@@ -83,6 +83,15 @@ Scheduler::Scheduler(const SchedulerConfig& cfg)
   L.bias_tok = take(L.bias_cap);
   L.bias_val = take(L.bias_cap);
   L.total = o;
+  L.rep_slot = take(L.max_seqs);
+  L.rep_reset = take(L.max_seqs);
+  L.rep_r = take(L.max_seqs);
+  L.rep_inv_r = take(L.max_seqs);
+  L.rep_start = take(L.max_seqs);
+  L.rep_n = take(L.max_seqs);
+  L.rep_cap = L.max_tokens + cfg.max_model_len;
+  L.rep_tok = take(L.rep_cap);
+  L.rep_total = o;
   for (int32_t r = L.max_seqs; r-- > 0;) embed_free_.push_back(r);
   for (int32_t r = std::max(0, std::min(cfg.max_num_seqs, cfg.penalty_slots)); r-- > 0;) pen_free_.push_back(r);
 }
@@ -93,7 +102,7 @@ void Scheduler::add_request(int64_t id, std::vector<int32_t> prompt, float tempe
                             int32_t top_k, float top_p, bool embed, bool embed_last, int32_t logprobs,
                             float presence_penalty, float frequency_penalty,
                             std::vector<std::pair<int32_t, float>> logit_bias, float min_p,
-                            float ln_min_p) {
+                            float ln_min_p, float repetition_penalty, float inv_repetition_penalty) {
   auto s = std::make_unique<Sequence>();
   s->id = id;
   if ((int32_t)prompt.size() >= cfg_.max_model_len)
@@ -136,6 +145,13 @@ void Scheduler::add_request(int64_t id, std::vector<int32_t> prompt, float tempe
       s->min_p = min_p;
       s->ln_min_p = ln_min_p;
     }
+  }
+  if (!embed && std::isfinite(repetition_penalty) && repetition_penalty > 0.f && repetition_penalty <= 2.f &&
+      repetition_penalty != 1.f) {
+    s->repetition_penalty = repetition_penalty;
+    rep_requested_ = true;
+    s->inv_repetition_penalty = (std::isfinite(inv_repetition_penalty) && inv_repetition_penalty > 0.f)
+                                    ? inv_repetition_penalty : (float)(1.0 / (double)repetition_penalty);
   }
   s->arrival = arrival_counter_++;
   // a grammar that starts with forced text (e.g. '{"key": ') is jump-forwarded into the prompt
@@ -226,9 +242,12 @@ void Scheduler::register_full_blocks(Sequence* s) {
   }
 }
 
-int32_t Scheduler::schedule(int32_t* buf) {
+int32_t Scheduler::schedule(int32_t* buf, int32_t buf_words) {
   const StepLayout& L = lay_;
   const int32_t B = cfg_.block_size;
+  if (rep_requested_ && buf_words < L.rep_total)  // before anything is planned or written
+    throw std::invalid_argument("scheduler: a request with a repetition penalty needs a step buffer of "
+                                "layout().rep_total words, stated as schedule()'s second argument");
   last_plan_.clear();
   int32_t tok_budget = cfg_.max_num_batched_tokens;
   int32_t prefill_budget = cfg_.max_prefill_tokens;
@@ -238,6 +257,13 @@ int32_t Scheduler::schedule(int32_t* buf) {
   auto pair_need = [](const Sequence* s, int32_t n) {
     return (s->penalised() && s->num_computed + n == (int32_t)s->tokens.size())
                ? (int32_t)s->tokens.size() - s->prompt_len - s->pen_synced : 0;
+  };
+  // the same for the repetition region: such a row samples only in a step that carries ALL the
+  // tokens (prompt and generated) its slot has not seen yet
+  int32_t rep_used = 0;
+  auto rep_need = [](const Sequence* s, int32_t n) {
+    return (s->repetitive() && s->num_computed + n == (int32_t)s->tokens.size())
+               ? (int32_t)s->tokens.size() - s->rep_synced : 0;
   };
 
   // 1) running sequences: decode tokens, jump-forward runs, unfinished prefill chunks.
@@ -265,6 +291,8 @@ int32_t Scheduler::schedule(int32_t* buf) {
     const int32_t n = std::min(pending, tok_budget);
     const int32_t pairs = pair_need(s, n);
     if (pair_used + pairs > L.pair_cap) continue;  // its new tokens do not fit the pair region: next step
+    const int32_t reps = rep_need(s, n);
+    if (rep_used + reps > L.rep_cap) continue;  // nor does its backlog fit the repetition region
     bool ok = ensure_blocks(s, s->num_computed + n);
     while (!ok) {
       // preempt the most recently arrived running sequence that is not yet planned
@@ -287,6 +315,7 @@ int32_t Scheduler::schedule(int32_t* buf) {
     last_plan_.push_back({s, n, !s->embed && s->num_computed + n == (int32_t)s->tokens.size()});
     tok_budget -= n;
     pair_used += pairs;
+    rep_used += reps;
   }
   running_.erase(std::remove_if(running_.begin(), running_.end(),
                                 [](Sequence* s) { return !s->running; }),
@@ -337,7 +366,7 @@ int32_t Scheduler::schedule(int32_t* buf) {
       embed_free_.pop_back();
     }
     // a penalised request without a free penalty slot waits (the requests behind it do not)
-    if (s->penalised() && s->pen_slot < 0 && pen_free_.empty()) {
+    if (s->needs_slot() && s->pen_slot < 0 && pen_free_.empty()) {
       waiting_.pop_front();
       deferred.push_back(s);
       continue;
@@ -346,7 +375,9 @@ int32_t Scheduler::schedule(int32_t* buf) {
     const int32_t pending = (int32_t)s->tokens.size() - s->num_computed;
     const int32_t n = std::min(pending, std::min(tok_budget, prefill_budget));
     const int32_t pairs = pair_need(s, n);
-    if (pair_used + pairs > L.pair_cap) {  // never with an empty step: one backlog always fits
+    const int32_t reps = rep_need(s, n);
+    // never with an empty step: one backlog always fits either region
+    if (pair_used + pairs > L.pair_cap || rep_used + reps > L.rep_cap) {
       waiting_.pop_front();
       deferred.push_back(s);
       continue;
@@ -356,12 +387,14 @@ int32_t Scheduler::schedule(int32_t* buf) {
     if (need > 0 && bm_.num_free() - need < (running_.empty() ? 0 : watermark)) break;
     if (!ensure_blocks(s, s->num_computed + n)) break;
     waiting_.pop_front();
-    if (s->penalised() && s->pen_slot < 0) {
+    if (s->needs_slot() && s->pen_slot < 0) {
       s->pen_slot = pen_free_.back();
       pen_free_.pop_back();
       s->pen_fresh = true;
+      s->rep_fresh = true;
     }
     pair_used += pairs;
+    rep_used += reps;
     s->running = true;
     s->preempted = false;
     running_.push_back(s);
@@ -440,6 +473,23 @@ int32_t Scheduler::schedule(int32_t* buf) {
   int32_t* btk = buf + L.bias_tok;
   float* bvl = reinterpret_cast<float*>(buf + L.bias_val);
   int32_t nbias = 0;
+  // repetition penalty: these regions are written only when a planned sampling row carries one
+  // and the grammar leaves it a choice, i.e. exactly in the steps that set bit 1 of counts[9]
+  bool any_rep = false;
+  for (const Planned& p : last_plan_) {
+    if (!p.sample || p.spec || !p.s->repetitive() || p.s->pen_slot < 0) continue;
+    int32_t cls = -1, forced = -1;
+    if (p.s->grammar) p.s->grammar->next(&cls, &forced);
+    any_rep = any_rep || forced < 0;
+  }
+  int32_t* rsl = buf + L.rep_slot;
+  int32_t* rrs = buf + L.rep_reset;
+  float* rrr = reinterpret_cast<float*>(buf + L.rep_r);
+  float* rir = reinterpret_cast<float*>(buf + L.rep_inv_r);
+  int32_t* rst = buf + L.rep_start;
+  int32_t* rnn = buf + L.rep_n;
+  int32_t* rtk = buf + L.rep_tok;
+  int32_t nrep = 0, nreptok = 0;
   const int32_t tpw = 16 / std::max(1, cfg_.gqa_group);
 
   int32_t T = 0, ns = 0, nsamp = 0, nit = 0, nparted = 0, pslot = 0;
@@ -598,6 +648,30 @@ int32_t Scheduler::schedule(int32_t* buf) {
           ++npen;
         }
       }
+      if (any_rep) {
+        rsl[nsamp] = -1;
+        rrs[nsamp] = 0;
+        rrr[nsamp] = rir[nsamp] = 1.f;
+        rst[nsamp] = nreptok;
+        rnn[nsamp] = 0;
+        // as above: a forced row is not touched and the device reads nothing for it; its
+        // backlog (the forced token included, once known) goes with the next free sampling row
+        if (s->repetitive() && s->pen_slot >= 0 && forced < 0 && !p.spec) {
+          const int32_t from = s->rep_synced, upto = (int32_t)s->tokens.size();
+          if (nreptok + (upto - from) > L.rep_cap)  // the planning above reserved this room
+            throw std::logic_error("scheduler: repetition token region overflows");
+          rsl[nsamp] = s->pen_slot;
+          rrs[nsamp] = s->rep_fresh ? 1 : 0;
+          rrr[nsamp] = s->repetition_penalty;
+          rir[nsamp] = s->inv_repetition_penalty;
+          rnn[nsamp] = upto - from;
+          std::memcpy(rtk + nreptok, s->tokens.data() + from, sizeof(int32_t) * (size_t)(upto - from));
+          nreptok += upto - from;
+          s->rep_synced = upto;
+          s->rep_fresh = false;
+          ++nrep;
+        }
+      }
       if (any_shape) {
         // stateless: every sampling row of a shaped sequence carries the request's list and
         // min_p -- speculative rows and rows after a preemption alike; the device skips a
@@ -699,6 +773,14 @@ int32_t Scheduler::schedule(int32_t* buf) {
       pst[r] = npair;
       pnn[r] = 0;
     }
+  if (any_rep)
+    for (int32_t r = nsamp; r < L.max_seqs; ++r) {
+      rsl[r] = -1;
+      rrs[r] = 0;
+      rrr[r] = rir[r] = 1.f;
+      rst[r] = nreptok;
+      rnn[r] = 0;
+    }
   if (any_shape)
     for (int32_t r = nsamp; r < L.max_seqs; ++r) {
       bst[r] = nbias;
@@ -720,6 +802,8 @@ int32_t Scheduler::schedule(int32_t* buf) {
   counts[7] = nembed;  // tokens whose hidden states are pooled (embedding requests)
   counts[8] = nlp;     // rows that need the log-probability pass
   counts[9] = npen > 0 ? 1 : 0;  // the step has a penalised sampling row (penalty pass)
+  // ... a row with a repetition penalty (repetition pass): bit 1, the rep_tok words in use above it
+  if (nrep > 0) counts[9] |= 2 | (nreptok << 2);
   counts[10] = npair;            // words of the pair region those rows use
   counts[11] = any_shape ? 1 + nbias : 0;  // a shaped sampling row (logit_bias / min_p pass) + its bias words
   if (nit > L.max_items)  // by construction (psz guard above, max_items sizing) this cannot happen
@@ -741,7 +825,7 @@ bool Scheduler::predict(Sequence* s, Planned& e) const {
   const int32_t ntok = (int32_t)s->tokens.size() + 1;
   if (ng >= s->max_tokens || ntok >= cfg_.max_model_len) return false;
   // penalty counts are sent as known tokens: a penalised row waits for its commit
-  if (s->penalised()) return false;
+  if (s->needs_slot()) return false;
   e.run.clear();
   if (!s->grammar) return true;
   const Grammar& g = *s->grammar;

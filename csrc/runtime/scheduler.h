@@ -78,8 +78,9 @@ struct SchedulerConfig {
   int32_t token_align = 0;
   int32_t kv_heads = 8;                // KV heads per rank (sizes the decode partitioning)
   int32_t align_slack = 96;
-  // device slots for presence / frequency penalty counts (csrc/ops/penalties.hip): a penalised
-  // request holds one from admission to finish; min(max_num_seqs, penalty_slots) exist
+  // device slots for presence / frequency penalty counts (csrc/ops/penalties.hip) and the
+  // repetition penalty's seen set (csrc/ops/repetition.hip): a request with either holds one
+  // from admission to finish; min(max_num_seqs, penalty_slots) exist
   int32_t penalty_slots = 64;
   std::vector<int32_t> eos_ids;
 };
@@ -110,6 +111,21 @@ struct StepLayout {
   int32_t bias_tok;    // [bias_cap]
   int32_t bias_val;    // [bias_cap]: fp32 bits
   int32_t bias_cap;    // max_seqs * LOGIT_BIAS_MAX: a step's lists always fit
+  // repetition penalty (csrc/ops/repetition.hip), after the shaping regions and behind `total`:
+  // written and copied only by steps with a sampling row that carries one. Such a step sets bit
+  // 1 of counts[9] and puts the words of rep_tok in use into the bits above it:
+  // counts[9] = [penalised row] | 2 | words << 2. `total` stays the extent of the regions above,
+  // all a scheduler that is never given a repetition_penalty writes; rep_total is the whole
+  // buffer, and schedule() refuses to write these regions into a buffer not stated to be that long.
+  int32_t rep_slot;   // [max_seqs]: slot of each sampling row (the request's penalty slot), -1 = none
+  int32_t rep_reset;  // [max_seqs]: 1 = the slot was just taken: clear its set first
+  int32_t rep_r;      // [max_seqs]: fp32 bits of r
+  int32_t rep_inv_r;  // [max_seqs]: fp32 bits of float32(1 / r), as submitted
+  int32_t rep_start;  // [max_seqs]: the row's new tokens (prompt and generated) are
+  int32_t rep_n;      // [max_seqs]:   rep_tok[rep_start : rep_start + rep_n]
+  int32_t rep_tok;    // [rep_cap]
+  int32_t rep_cap;    // max_tokens + max_model_len: one whole backlog always fits
+  int32_t rep_total;
 };
 
 constexpr int32_t LOGIT_BIAS_MAX = 300;  // entries of one request's logit_bias
@@ -181,6 +197,16 @@ struct Sequence {
   std::vector<std::pair<int32_t, float>> logit_bias;
   float min_p = 0.f, ln_min_p = 0.f;
   bool shaped() const { return !embed && (!logit_bias.empty() || min_p > 0.f); }
+  // repetition penalty r in (0, 2], 1 = off, with the float32(1 / r) the host computed at submit.
+  // The device keeps the set of distinct ids of tokens[0:] -- the prompt too, whatever part of it
+  // the prefix cache serves -- in the request's penalty slot (the same index as the additive
+  // penalties' counts, separate arrays); rep_synced of those tokens have been sent to it;
+  // rep_fresh: the slot's old set is not cleared yet
+  float repetition_penalty = 1.f, inv_repetition_penalty = 1.f;
+  int32_t rep_synced = 0;
+  bool rep_fresh = false;
+  bool repetitive() const { return !embed && repetition_penalty != 1.f; }
+  bool needs_slot() const { return penalised() || repetitive(); }
   bool ignore_eos = false;
   std::vector<int32_t> stop_ids;
   int64_t arrival = 0;
@@ -217,7 +243,8 @@ class Scheduler {
                    bool embed = false, bool embed_last = false, int32_t logprobs = -1,
                    float presence_penalty = 0.f, float frequency_penalty = 0.f,
                    std::vector<std::pair<int32_t, float>> logit_bias = {}, float min_p = 0.f,
-                   float ln_min_p = 0.f);
+                   float ln_min_p = 0.f, float repetition_penalty = 1.f,
+                   float inv_repetition_penalty = 0.f);  // 0: float32(1 / r) is computed here
   bool abort(int64_t id);
   // Fill `buf` (layout()) for the next step. Returns the number of tokens in the
   // step (0 = nothing to run).
@@ -232,7 +259,13 @@ class Scheduler {
   // EOS. commit() of the in-flight step checks the guess; a wrong guess voids the row's
   // speculative entry (its sample is dropped, its KV beyond the pending token is
   // recomputed) — only the sampled token's own KV is kept, and it is always right.
-  int32_t schedule(int32_t* buf);
+  //
+  // `buf_words`: the size of `buf` in 32-bit words, 0 = not stated. layout().total covers every
+  // region except the repetition penalty's, which lie behind it (layout().rep_total is the whole
+  // buffer). Once a request with a repetition penalty has been added, schedule() throws
+  // std::invalid_argument unless buf_words >= layout().rep_total, so a caller that sized its buffer by `total` and then adds a
+  // request with a repetition penalty gets an error, never a write past its buffer.
+  int32_t schedule(int32_t* buf, int32_t buf_words = 0);
   // Consume the sampled tokens of the oldest uncommitted step (one per sampling row).
   // `lp`: the step's log-probability records, one per sampling row (nullptr: the step computed
   // none); rows of requests that did not ask hold nothing meaningful and are not read.
@@ -307,6 +340,7 @@ class Scheduler {
   std::vector<int32_t> embed_free_;    // free pooling rows (0 .. max_seqs - 1)
   std::vector<int32_t> embed_resets_;  // rows of preempted embedding requests, to be cleared
   std::vector<int32_t> pen_free_;      // free penalty slots
+  bool rep_requested_ = false;         // a request with a repetition penalty was added: see schedule()
   int64_t arrival_counter_ = 0;
   int64_t stat_prompt_tokens_ = 0, stat_cached_tokens_ = 0, stat_preemptions_ = 0, stat_steps_ = 0;
   int64_t stat_aligned_steps_ = 0;

@@ -85,6 +85,9 @@ class LLMConfig(BaseModel):
     # min_p truncation, the request default (0 = off): at temperature > 0 keep the tokens whose
     # probability is at least min_p times the most likely one's
     min_p: float = Field(default=0.0, ge=0.0, le=1.0)
+    # multiplicative repetition penalty over the prompt and the reply so far (the HF / vLLM rule),
+    # the request default (1 = off)
+    repetition_penalty: float = Field(default=1.0, gt=0.0, le=2.0)
     max_tokens: int = Field(default=2000, gt=0)
     function_calling_model: Optional[str] = None
     system_template: Optional[str] = None

@@ -46,6 +46,7 @@ import torch
 from pilottai_amd import ops
 from pilottai_amd.engine.tp_sampling import tp_topkp_threshold
 from pilottai_amd.models.llama import KVCache, LlamaModel, StepMeta, get_config
+from pilottai_amd.ops.reference import inv_repetition_penalty as ref_inv_repetition_penalty
 from pilottai_amd.ops.reference import ln_min_p as ref_ln_min_p
 from pilottai_amd.parallel.comm import TPGroup
 from pilottai_amd.utils.tracing import trace_range
@@ -216,6 +217,8 @@ class _Request:
     logit_bias: tuple = ()          # ((token id, bias), ...): unique ids, non-zero values in [-100, 100]
     min_p: float = 0.0              # 0 off; else in (0, 1]
     ln_min_p: float = 0.0           # float32(ln min_p), computed once here for host and device
+    repetition_penalty: float = 1.0      # 1 off; else in (0, 2]
+    inv_repetition_penalty: float = 1.0  # float32(1 / r), computed once here for host and device
 
 
 class LLMEngine:
@@ -322,11 +325,11 @@ class LLMEngine:
         # one being scheduled); the device copy is stream-ordered behind the previous step
         self._async = bool(cfg.async_steps) and self.tp.size == 1
         nbuf = 2 if self._async else 1
-        self._host_metas = [torch.zeros(L["total"], dtype=torch.int32, pin_memory=pin) for _ in range(nbuf)]
+        self._host_metas = [torch.zeros(L["rep_total"], dtype=torch.int32, pin_memory=pin) for _ in range(nbuf)]
         self._host_meta = self._host_metas[0]
         self._host_ptr = self._host_meta.data_ptr()
         self._host_np = self._host_meta.numpy()
-        self._dev_meta = torch.zeros(L["total"], dtype=torch.int32, device=self.device) \
+        self._dev_meta = torch.zeros(L["rep_total"], dtype=torch.int32, device=self.device) \
             if (self.on_gpu or self._async) else self._host_meta
         # attention tickets: one per (sequence, KV head) for split decode rows, then -- only with
         # prefill_split_keys on -- one per (partial slot, KV head) for split prefill items
@@ -390,11 +393,17 @@ class LLMEngine:
         # rewrites the logits behind the LM head in the step graph's penalty variant
         self._pen_slots = max(0, min(int(cfg.max_num_seqs), int(cfg.penalty_slots)))
         self._pen_state = None
+        # repetition penalty (submit(repetition_penalty=)): the seen set of each slot (the same
+        # slot indices, separate arrays), allocated on the first such request;
+        # ops.apply_repetition_penalty is the first pass behind the LM head in the step graph's
+        # repetition variant
+        self._rep_state = None
         # one graph per (token bucket, top-k/top-p pass, embedding pooling); truncating variants
         # are captured on first use, so steps without truncation pay nothing for it. The variant
         # with the log-probability pass has the 4-tuple key (bucket, trunc, embed, True), a step
         # with a penalised row the 5-tuple key (bucket, trunc, embed, lp, True), a step with a
-        # logit_bias / min_p row the 6-tuple key (bucket, trunc, embed, lp, pen, True).
+        # logit_bias / min_p row the 6-tuple key (bucket, trunc, embed, lp, pen, True), a step
+        # with a repetition-penalty row the 7-tuple key (bucket, trunc, embed, lp, pen, shape, True).
         self._graphs: Dict[tuple, "torch.cuda.CUDAGraph"] = {}
         self._tau = torch.empty(S, dtype=torch.float32, device=self.device)
         self._graph_pool = None
@@ -496,6 +505,13 @@ class LLMEngine:
         self._ln_minp = sl("ln_minp", ms).view(torch.float32)
         self._bias_tok = sl("bias_tok", L["bias_cap"])
         self._bias_val = sl("bias_val", L["bias_cap"]).view(torch.float32)
+        self._rep_slot = sl("rep_slot", ms)
+        self._rep_reset = sl("rep_reset", ms)
+        self._rep_r = sl("rep_r", ms).view(torch.float32)
+        self._rep_inv_r = sl("rep_inv_r", ms).view(torch.float32)
+        self._rep_start = sl("rep_start", ms)
+        self._rep_n = sl("rep_n", ms)
+        self._rep_tok = sl("rep_tok", L["rep_cap"])
 
     def _sync_masks(self) -> bool:
         reg = self.grammar.reg
@@ -522,13 +538,24 @@ class LLMEngine:
             self._pen_state = ops.penalty_state(self._pen_slots, self.model.v_local, self.max_model_len,
                                                 self.device)
 
+    def _ensure_rep_state(self):
+        """Allocate the slots' seen sets (engine thread, never inside a capture)."""
+        if self._rep_state is None:
+            self._rep_state = ops.repetition_state(self._pen_slots, self.model.v_local, self.max_model_len,
+                                                   self.device)
+
     def _forward_and_sample(self, bucket: int, s_b: int, ns: int, trunc: bool = False, embed: bool = False,
-                            lp: bool = False, pen: bool = False, shape: bool = False):
+                            lp: bool = False, pen: bool = False, shape: bool = False, rep: bool = False):
         meta = self._meta_for(bucket, s_b, ns)
         if self._async:  # pending tokens of rows that sampled in the previous step
             ops.patch_pending_ids(meta.input_ids[:bucket], self._sampled_dev)
         logits = self.model.forward(meta, self.kv, bucket, s_b, self._part_o, self._part_ml,
                                     embed=(self._embed_rows, self._embed_pool) if embed else None)
+        if rep:
+            # on the raw logits, before the additive penalties and everything else
+            ops.apply_repetition_penalty(logits, self._rep_state, self._rep_slot[:s_b], self._rep_reset[:s_b],
+                                         self._rep_r[:s_b], self._rep_inv_r[:s_b], self._forced[:s_b],
+                                         self._rep_start[:s_b], self._rep_n[:s_b], self._rep_tok)
         if pen:
             # before anything reads the logits: the threshold, the sampler and the logprob pass
             # all see the penalised distribution
@@ -583,7 +610,9 @@ class LLMEngine:
 
     @staticmethod
     def _graph_key(bucket: int, trunc: bool, embed: bool, lp: bool = False, pen: bool = False,
-                   shape: bool = False) -> tuple:
+                   shape: bool = False, rep: bool = False) -> tuple:
+        if rep:
+            return (bucket, trunc, embed, lp, pen, shape, True)
         if shape:
             return (bucket, trunc, embed, lp, pen, True)
         if pen:
@@ -591,24 +620,26 @@ class LLMEngine:
         return (bucket, trunc, embed, True) if lp else (bucket, trunc, embed)
 
     def _run(self, bucket: int, ns: int, trunc: bool, n_copy: int, embed: bool = False, lp: bool = False,
-             pen: bool = False, shape: bool = False):
-        """Replay the (bucket, trunc, embed[, logprobs[, penalties[, shaping]]]) graph — capturing
-        it first if needed — or run eagerly."""
+             pen: bool = False, shape: bool = False, rep: bool = False):
+        """Replay the (bucket, trunc, embed[, logprobs[, penalties[, shaping[, repetition]]]]) graph
+        — capturing it first if needed — or run eagerly."""
         if pen:
             self._ensure_pen_state()
+        if rep:
+            self._ensure_rep_state()
         if not self.use_graphs:
-            self._forward_and_sample(bucket, self._seq_bucket(bucket), ns, trunc, embed, lp, pen, shape)
+            self._forward_and_sample(bucket, self._seq_bucket(bucket), ns, trunc, embed, lp, pen, shape, rep)
             return
-        key = self._graph_key(bucket, trunc, embed, lp, pen, shape)
+        key = self._graph_key(bucket, trunc, embed, lp, pen, shape, rep)
         g = self._graphs.get(key)
         if g is None:
-            if shape:  # the shaping regions lie behind the copied prefix: keep the whole buffer
-                n_copy = self.L["total"]
+            if shape or rep:  # their regions lie behind the copied prefix: keep the whole buffer
+                n_copy = self.L["rep_total"]
             saved = self._dev_meta[:n_copy].clone()
             pool = self._embed_pool.clone()
             samp = self._sampled_dev.clone()  # the previous step's tokens (pipelined mode)
             self.capture_graphs([bucket], trunc=trunc, embed=embed, lp=lp, pen=pen,
-                                shape=shape)  # clobbers the device metadata
+                                shape=shape, rep=rep)  # clobbers the device metadata
             self.stats["graph_captures"] += 1  # a first-use capture inside serving (tens of ms)
             self._dev_meta[:n_copy].copy_(saved)
             self._embed_pool.copy_(pool)
@@ -627,17 +658,24 @@ class LLMEngine:
             a = L["bias_val"]
             self._dev_meta[a:a + n_bias].copy_(hm[a:a + n_bias], non_blocking=self.on_gpu)
 
+    def _copy_repetition(self, hm: torch.Tensor, n_tok: int):
+        """Host -> device copy of the repetition regions of a step with such a row: the per-row
+        words and the `n_tok` token words in use, one piece."""
+        a, b = self.L["rep_slot"], self.L["rep_tok"] + n_tok
+        self._dev_meta[a:b].copy_(hm[a:b], non_blocking=self.on_gpu)
+
     def _seq_bucket(self, bucket: int) -> int:
         return min(bucket, self.cfg.max_num_seqs)
 
     def _dummy_meta(self):
         """A metadata state under which a forward touches no KV and no attention item."""
         L = self.L
-        d = torch.zeros(L["total"], dtype=torch.int32)
+        d = torch.zeros(L["rep_total"], dtype=torch.int32)
         d[L["slots"]:L["slots"] + L["max_tokens"]] = -1
         d[L["embed_rows"]:L["embed_rows"] + L["max_tokens"]] = L["max_seqs"]
         d[L["pen_slot"]:L["pen_slot"] + L["max_seqs"]] = -1  # the penalty pass touches nothing
         # bias_n = 0 and min_p = 0 (the zeros above): the logit_bias / min_p passes touch nothing
+        d[L["rep_slot"]:L["rep_slot"] + L["max_seqs"]] = -1  # the repetition pass touches nothing
         self._dev_meta.copy_(d.to(self.device))
 
     def capture_embed_graphs(self):
@@ -648,20 +686,22 @@ class LLMEngine:
         self.capture_graphs(embed=True)
 
     def capture_graphs(self, buckets: Optional[Sequence[int]] = None, trunc: bool = False, embed: bool = False,
-                       lp: bool = False, pen: bool = False, shape: bool = False):
+                       lp: bool = False, pen: bool = False, shape: bool = False, rep: bool = False):
         """Capture one hipGraph per token bucket (shared memory pool); the top-k/top-p,
-        embedding-pooling, log-probability, penalty and logit_bias / min_p (`shape`) variants
-        are captured on first use, or up front by a call with the flag set."""
+        embedding-pooling, log-probability, penalty, logit_bias / min_p (`shape`) and repetition
+        penalty (`rep`) variants are captured on first use, or up front by a call with the flag set."""
         if not self.use_graphs:
             return
         if pen:
             self._ensure_pen_state()
+        if rep:
+            self._ensure_rep_state()
         self._dummy_meta()
         if self._graph_pool is None:
             self._graph_pool = torch.cuda.graph_pool_handle()
         t0 = time.time()
         for b in sorted(buckets or self.buckets, reverse=True):
-            key = self._graph_key(b, trunc, embed, lp, pen, shape)
+            key = self._graph_key(b, trunc, embed, lp, pen, shape, rep)
             if key in self._graphs:
                 continue
             s_b = self._seq_bucket(b)
@@ -669,11 +709,11 @@ class LLMEngine:
             st.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(st):
                 for _ in range(2):
-                    self._forward_and_sample(b, s_b, 0, trunc, embed, lp, pen, shape)
+                    self._forward_and_sample(b, s_b, 0, trunc, embed, lp, pen, shape, rep)
             torch.cuda.current_stream().wait_stream(st)
             g = torch.cuda.CUDAGraph(keep_graph=True) if self.cfg.keep_graphs else torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, pool=self._graph_pool):
-                self._forward_and_sample(b, s_b, 0, trunc, embed, lp, pen, shape)
+                self._forward_and_sample(b, s_b, 0, trunc, embed, lp, pen, shape, rep)
             if self.cfg.keep_graphs:
                 g.instantiate()
             self._graphs[key] = g
@@ -717,13 +757,21 @@ class LLMEngine:
             raise ValueError(f"min_p must be a number in [0, 1], not {v!r}")
         return float(v)
 
+    @staticmethod
+    def check_repetition_penalty(repetition_penalty) -> float:
+        """Validate `repetition_penalty` (None = 1 = off): a finite number in (0, 2], else ValueError."""
+        v = 1.0 if repetition_penalty is None else repetition_penalty
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 < v <= 2.0:  # NaN fails too
+            raise ValueError(f"repetition_penalty must be a number in (0, 2], not {v!r}")
+        return float(v)
+
     def submit(self, prompt_ids: Sequence[int], callback: Callable[[GenerationOutput], None], *,
                temperature: float = 0.7, max_tokens: int = 256, seed: Optional[int] = None,
                ignore_eos: bool = False, stop_ids: Sequence[int] = (), grammar: Optional[list] = None,
                request_id: Optional[int] = None, top_k: int = 0, top_p: float = 1.0,
                embed: Union[bool, str] = False, logprobs: int = -1, presence_penalty: float = 0.0,
                frequency_penalty: float = 0.0, logit_bias: Optional[Mapping[int, float]] = None,
-               min_p: float = 0.0) -> int:
+               min_p: float = 0.0, repetition_penalty: float = 1.0) -> int:
         """Thread-safe; `callback` runs on the engine thread when the request finishes.
 
         top_k > 0 / top_p < 1 truncate the (grammar-masked) distribution before
@@ -755,7 +803,17 @@ class LLMEngine:
         probability >= p * the largest), intersected with top_k / top_p; greedy rows and logprobs
         ignore it. Both are stateless on the device: they work with async_steps and across
         preemption. An empty bias with min_p = 0 is exactly the request without them. Not for
-        embedding requests, not on a TP > 1 engine."""
+        embedding requests, not on a TP > 1 engine.
+
+        repetition_penalty r in (0, 2] (1 off), the HF / vLLM rule with 1 / r rounded once to
+        float32: at every sampling step, on the raw logits before the additive penalties, every
+        token t that occurs in the prompt (whatever part of it the prefix cache served) or among
+        the tokens generated so far (sampled and grammar-forced) gets logit[t] <- bf16(x > 0 ?
+        x * float32(1 / r) : x * r), x = float(logit[t]); a row whose token the grammar forces is
+        not touched. Greedy rows are penalised, logprobs are those of the penalised distribution.
+        The request holds a penalty slot (shared with its additive penalties); its tokens do not
+        depend on what it is batched with and survive preemption. Not for embedding requests, not
+        on a TP > 1 engine, not with async_steps."""
         if self._err is not None:
             raise RuntimeError(f"engine failed: {self._err!r}")
         logprobs = -1 if logprobs is None else int(logprobs)
@@ -787,13 +845,24 @@ class LLMEngine:
                 raise ValueError("logit_bias / min_p are not available on embedding requests")
             if self.tp.size > 1:
                 raise ValueError("logit_bias / min_p are not supported on a tensor-parallel (TP > 1) engine")
+        rep_r = self.check_repetition_penalty(repetition_penalty)
+        if rep_r != 1.0:
+            if embed:
+                raise ValueError("repetition_penalty is not available on embedding requests")
+            if self.tp.size > 1:
+                raise ValueError("repetition_penalty is not supported on a tensor-parallel (TP > 1) engine")
+            if self.cfg.async_steps:
+                raise ValueError("repetition_penalty is not supported on an async_steps engine")
+            if self._pen_slots < 1:
+                raise ValueError("repetition_penalty needs EngineConfig.penalty_slots >= 1")
         rid = request_id if request_id is not None else self.new_request_id()
         if seed is None:
             seed = (self.cfg.seed * 0x9E3779B1 + rid * 0x85EBCA77) & 0x7FFFFFFFFFFFFFFF
         req = _Request(rid, list(prompt_ids), float(temperature), int(max_tokens), int(seed),
                        bool(ignore_eos), list(stop_ids), grammar, callback, self._rt.now(),
                        int(top_k or 0), float(1.0 if top_p is None else top_p), bool(embed), embed == "last",
-                       logprobs, pens[0], pens[1], bias, min_p, ref_ln_min_p(min_p))
+                       logprobs, pens[0], pens[1], bias, min_p, ref_ln_min_p(min_p), rep_r,
+                       ref_inv_repetition_penalty(rep_r))
         self._inbox.put(req)
         self._wake.set()
         return rid
@@ -1026,7 +1095,8 @@ class LLMEngine:
             self.sched.add_request(req.rid, req.prompt_ids, req.temperature, req.max_tokens, req.seed,
                                    req.ignore_eos, req.stop_ids, req.grammar, req.top_k, req.top_p, req.embed,
                                    req.embed_last, req.logprobs, req.presence_penalty, req.frequency_penalty,
-                                   list(req.logit_bias), req.min_p, req.ln_min_p)
+                                   list(req.logit_bias), req.min_p, req.ln_min_p, req.repetition_penalty,
+                                   req.inv_repetition_penalty)
             self.stats["requests"] += 1
         while True:
             try:
@@ -1077,7 +1147,7 @@ class LLMEngine:
         L = self.L
         t0 = time.perf_counter()
         with trace_range("engine.schedule"):
-            T = self.sched.schedule(self._host_ptr)
+            T = self.sched.schedule(self._host_ptr, self._host_meta.numel())
         t_sched = time.perf_counter()
         if T == 0:
             self._flush_deliveries()
@@ -1086,7 +1156,8 @@ class LLMEngine:
             return False
         c = self._host_np[L["counts"]:L["counts"] + 12]
         ns, nsamp, trunc, embed, lp = int(c[1]), int(c[2]), int(c[6]) > 0, int(c[7]) > 0, int(c[8]) > 0
-        pen = int(c[9]) > 0
+        pen = (int(c[9]) & 1) > 0
+        rep = int(c[9]) >> 1  # 0, or 1 + 2 * the token words of the step's repetition-penalty rows
         shape = int(c[11])  # 0, or 1 + the bias words of the step's logit_bias / min_p rows
         bucket = next(b for b in self.buckets if b >= T)
         s_b = self._seq_bucket(bucket)
@@ -1101,13 +1172,15 @@ class LLMEngine:
             self._dev_meta[:n_copy].copy_(self._host_meta[:n_copy], non_blocking=True)
             if shape:
                 self._copy_shaping(self._host_meta, shape - 1)
+            if rep:
+                self._copy_repetition(self._host_meta, rep >> 1)
         if self.tp.size > 1:
             self._tp_send(_OP_STEP, T, ns, nsamp, bucket, int(masks_changed), n_copy, int(trunc), int(embed))
             if masks_changed:
                 self.tp.broadcast(self._class_masks)
             self.tp.broadcast(self._dev_meta[:n_copy])
         with torch.inference_mode(), trace_range("engine.forward"):
-            self._run(bucket, ns, trunc, n_copy, embed, lp, pen, shape > 0)
+            self._run(bucket, ns, trunc, n_copy, embed, lp, pen, shape > 0, rep > 0)
         if self._step_listeners:
             self._notify_launch(T)
         if nsamp:
@@ -1174,7 +1247,7 @@ class LLMEngine:
         hm = self._host_metas[slot]
         t0 = time.perf_counter()
         with trace_range("engine.schedule"):
-            T = self.sched.schedule(hm.data_ptr())
+            T = self.sched.schedule(hm.data_ptr(), hm.numel())
         t_sched = time.perf_counter()
         if T == 0:
             if not self._inflight and self.sched.num_running == 0 and self.sched.num_waiting > 0:

@@ -16,7 +16,8 @@ OpenAI-compatible server, pass `schema_mode="json_object"` to send
 `response_format["presence_penalty"]` / `["frequency_penalty"]` (or the `LLMConfig` defaults of
 the same names) are sent under their OpenAI names when non-zero. `response_format["logit_bias"]`
 ({token id: bias}) is sent in the OpenAI wire form (keys as strings), `response_format["min_p"]`
-(default `LLMConfig.min_p`) as `min_p` when non-zero.
+(default `LLMConfig.min_p`) as `min_p` when non-zero, `response_format["repetition_penalty"]`
+(default `LLMConfig.repetition_penalty`) as `repetition_penalty` when it is not 1.
 
     LLMConfig(provider="openai", base_url="http://10.0.0.5:8000/v1", api_key=...)
 """
@@ -32,6 +33,7 @@ class OpenAICompatLLM(BaseLLM):
     supports_logprobs = True
     supports_penalties = True
     supports_logit_shaping = True
+    supports_repetition_penalty = True
 
     def __init__(self, config: Any = None, base_url: Optional[str] = None, timeout_s: float = 600.0,
                  schema_mode: str = "pilottai"):
@@ -77,6 +79,9 @@ class OpenAICompatLLM(BaseLLM):
         mp = rf.get("min_p", self.min_p)
         if mp:
             body["min_p"] = float(mp)
+        rp = rf.get("repetition_penalty", self.repetition_penalty)
+        if rp is not None and float(rp) != 1.0:
+            body["repetition_penalty"] = float(rp)
         if tools:
             body["tools"] = self._format_tools(tools)
         elif rf.get("schema") is not None:

@@ -114,6 +114,7 @@ class BaseLLM:
     supports_penalties = False
     # response_format["logit_bias"] ({token id: bias}) / ["min_p"] are honoured
     supports_logit_shaping = False
+    supports_repetition_penalty = False  # response_format["repetition_penalty"] is honoured
 
     def __init__(self, config: Any = None):
         self.config = config
@@ -126,6 +127,9 @@ class BaseLLM:
         self.frequency_penalty = float(_cfg_get(config, "frequency_penalty", 0.0) or 0.0)
         # request default of min_p truncation (0 = off); a logit_bias has no config default
         self.min_p = float(_cfg_get(config, "min_p", 0.0) or 0.0)
+        # request default of the multiplicative repetition penalty (1 = off)
+        rp = _cfg_get(config, "repetition_penalty", 1.0)
+        self.repetition_penalty = 1.0 if rp is None else float(rp)
         self.max_tokens = int(_cfg_get(config, "max_tokens", 2000))
         self.retry_attempts = max(1, int(_cfg_get(config, "retry_attempts", 3)))
         self.retry_delay = float(_cfg_get(config, "retry_delay", 1.0))
@@ -200,6 +204,7 @@ class LocalLLM(BaseLLM):
     supports_logprobs = True
     supports_penalties = True
     supports_logit_shaping = True
+    supports_repetition_penalty = True
     prefix_cache_layout = True  # agents put the shared task text first (core/agent.py)
 
     def __init__(self, config: Any = None, engine=None):
@@ -246,7 +251,8 @@ class LocalLLM(BaseLLM):
                                  logprobs=-1 if rf.get("logprobs") is None else int(rf["logprobs"]),
                                  presence_penalty=rf.get("presence_penalty", self.presence_penalty),
                                  frequency_penalty=rf.get("frequency_penalty", self.frequency_penalty),
-                                 logit_bias=rf.get("logit_bias"), min_p=rf.get("min_p", self.min_p))
+                                 logit_bias=rf.get("logit_bias"), min_p=rf.get("min_p", self.min_p),
+                                 repetition_penalty=rf.get("repetition_penalty", self.repetition_penalty))
         try:
             out = await fut
         except asyncio.CancelledError:

@@ -272,6 +272,39 @@ def apply_penalties(logits, state, pen_slot, pen_reset, presence, frequency, for
     return logits
 
 
+REPETITION_LAUNCHES = 1  # kernels apply_repetition_penalty() launches on the GPU
+
+
+def repetition_state(slots: int, V: int, cap: int, device):
+    """Zeroed device state of `slots` repetition-penalty slots: (seen int32 [slots, ceil(V / 32)]
+    -- bit t & 31 of word t >> 5 = token t occurred --, seen_list int32 [slots, cap] -- the
+    tokens that occurred, each once -- and n_seen int32 [slots])."""
+    return (torch.zeros(slots, (V + 31) // 32, dtype=torch.int32, device=device),
+            torch.zeros(slots, cap, dtype=torch.int32, device=device),
+            torch.zeros(slots, dtype=torch.int32, device=device))
+
+
+def apply_repetition_penalty(logits, state, rep_slot, rep_reset, rep_r, rep_inv_r, forced, rep_start, rep_n,
+                             rep_tok):
+    """Repetition penalty, in place on `logits` [rows, V] bf16 (csrc/ops/repetition.hip).
+
+    Row i with slot s = rep_slot[i] >= 0 and forced[i] < 0: if rep_reset[i], the slot's set is
+    cleared first; the tokens rep_tok[rep_start[i] : rep_start[i] + rep_n[i]] join the slot's
+    set (ids outside [0, V) are skipped, a window that leaves rep_tok is not applied); then every
+    token t of the set gets logit[t] <- bf16(x > 0 ? x * rep_inv_r[i] : x * rep_r[i]) with
+    x = float(logit[t]) -- one correctly rounded fp32 product, one round-to-nearest-even
+    conversion. Every other row, and the state of its slot, is untouched.
+    `state` = repetition_state(...), updated in place. A slot may appear in one row only."""
+    seen, seen_list, n_seen = state
+    if _on_gpu(logits):
+        require_native().apply_repetition_penalty(logits, seen, seen_list, n_seen, rep_slot, rep_reset, rep_r,
+                                                  rep_inv_r, forced, rep_start, rep_n, rep_tok)
+        return logits
+    ref.apply_repetition_penalty(logits, state, rep_slot, rep_reset, rep_r, rep_inv_r, forced, rep_start, rep_n,
+                                 rep_tok)
+    return logits
+
+
 LOGIT_BIAS_MAX = 300        # entries of one request's logit_bias (the OpenAI API's bound)
 LOGIT_BIAS_LAUNCHES = 1     # kernels apply_logit_bias() launches on the GPU
 MINP_THRESHOLD_LAUNCHES = 1  # kernels minp_threshold() launches on the GPU

@@ -317,6 +317,57 @@ def apply_penalties(logits: torch.Tensor, state, pen_slot, pen_reset, presence, 
     return logits
 
 
+def inv_repetition_penalty(r: float) -> float:
+    """float32(1 / r), the form in which a request's repetition penalty divides on the device:
+    computed in double precision, rounded once. 1.0 for r = 1 (off)."""
+    return float(np.float32(1.0 / np.float64(r)))
+
+
+def apply_repetition_penalty(logits: torch.Tensor, state, rep_slot, rep_reset, rep_r, rep_inv_r, forced,
+                             rep_start, rep_n, rep_tok):
+    """Repetition penalty in place on `logits` [rows, V] (see ops.apply_repetition_penalty), with
+    the device kernel's data flow: the slot's list is walked to clear its membership words, the
+    row's new tokens are appended when their bit flips, and the logits of the listed tokens are
+    rewritten with one fp32 product and one conversion back to the logits' dtype."""
+    seen, seen_list, n_seen = state
+    rows, V = logits.shape
+    slots, cap = seen_list.shape
+    bits = seen.numpy().view(np.uint32)  # shares the tensor's memory
+    for i in range(rows):
+        s = int(rep_slot[i])
+        if s < 0 or s >= slots or int(forced[i]) >= 0:
+            continue
+        if int(rep_reset[i]) != 0:
+            n_old = min(max(int(n_seen[s]), 0), cap)
+            for t in seen_list[s, :n_old].tolist():
+                if 0 <= t < V:
+                    bits[s, t >> 5] = 0
+            n_seen[s] = 0
+        a0, n_new = int(rep_start[i]), int(rep_n[i])
+        if a0 < 0 or n_new < 0 or a0 + n_new > rep_tok.numel():
+            n_new = 0
+        for t in rep_tok[a0:a0 + n_new].tolist():
+            if not 0 <= t < V:
+                continue
+            w, b = t >> 5, np.uint32(1 << (t & 31))
+            if bits[s, w] & b:
+                continue
+            bits[s, w] |= b
+            at = int(n_seen[s])
+            if at < cap:
+                seen_list[s, at] = t
+            n_seen[s] = at + 1
+        n = min(max(int(n_seen[s]), 0), cap)
+        if n == 0:
+            continue
+        idx = seen_list[s, :n].long()
+        idx = idx[(idx >= 0) & (idx < V)]
+        x = logits[i, idx].float()
+        y = torch.where(x > 0, x * rep_inv_r[i].float(), x * rep_r[i].float())  # fp32 products, correctly rounded
+        logits[i, idx] = y.to(logits.dtype)
+    return logits
+
+
 def apply_logit_bias(logits: torch.Tensor, bias_start, bias_n, bias_tok, bias_val, forced):
     """logit_bias in place on `logits` [rows, V] (see ops.apply_logit_bias): one fp32 add per
     listed token, one conversion back to the logits' dtype."""

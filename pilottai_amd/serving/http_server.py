@@ -29,7 +29,9 @@ grammar-forced token has 0.0). Each entry also carries `token_id`; -inf is sent 
 `presence_penalty` / `frequency_penalty` (numbers in [-2, 2], OpenAI semantics over the
 GENERATED tokens: logit[t] -= presence * [c_t > 0] + frequency * c_t) are applied by the engine
 before the grammar mask, top-k / top-p, the sampler and the logprob pass; 0 or absent means
-nothing. A multiplicative `repetition_penalty` and `n > 1` are not supported.
+nothing. `repetition_penalty` (a number in (0, 2], the HF / vLLM extension; 1 or absent means
+nothing) is applied before them, on the raw logits: every token t of the prompt or of the reply so
+far gets logit[t] <- x > 0 ? x * float32(1 / r) : x * r. `n > 1` is not supported.
 
 `logit_bias` (the OpenAI wire form: an object of at most 300 entries whose keys are token ids
 as strings and whose values are numbers in [-100, 100]) is added to those logits at every
@@ -138,6 +140,16 @@ def _penalties(body: Dict[str, Any]) -> Dict[str, float]:
         if v != 0:
             out[k] = float(v)
     return out
+
+
+def _repetition(body: Dict[str, Any]) -> Dict[str, float]:
+    """The request's `repetition_penalty` when it is not 1 (1 or absent: nothing)."""
+    v = body.get("repetition_penalty")
+    if v is None:
+        return {}
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 < v <= 2.0:  # NaN fails too
+        raise ValueError("repetition_penalty must be a number greater than 0 and at most 2")
+    return {"repetition_penalty": float(v)} if v != 1 else {}
 
 
 LOGIT_BIAS_MAX = 300  # entries of one request's logit_bias (ops.LOGIT_BIAS_MAX)
@@ -256,6 +268,7 @@ def create_app(llm, model_name: Optional[str] = None, engine=None) -> FastAPI:
             tools = _tools(body)
             n_lp = _logprobs(body)
             pens = _penalties(body)
+            rep = _repetition(body)
             eng = engine or getattr(llm, "engine", None)
             shaping = _shaping(body, getattr(getattr(eng, "model_cfg", None), "vocab_size", None))
         except (KeyError, ValueError) as e:
@@ -265,6 +278,11 @@ def create_app(llm, model_name: Optional[str] = None, engine=None) -> FastAPI:
                 raise HTTPException(400, f"the {getattr(llm, 'provider', 'configured')} backend cannot apply "
                                          "logit_bias / min_p")
             rf = dict(rf or {}, **shaping)
+        if rep:
+            if not getattr(llm, "supports_repetition_penalty", False):
+                raise HTTPException(400, f"the {getattr(llm, 'provider', 'configured')} backend cannot apply "
+                                         "a repetition_penalty")
+            rf = dict(rf or {}, **rep)
         if pens:
             if not getattr(llm, "supports_penalties", False):
                 raise HTTPException(400, f"the {getattr(llm, 'provider', 'configured')} backend cannot apply "
