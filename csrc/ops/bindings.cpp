@@ -31,6 +31,10 @@ int pa_token_logprobs(float* out_lp, int out_stride, int* top_ids, float* top_lp
                       const void* logits, int rows, int V, int ld, const int* tokens, const int* lp_n,
                       const int* forced, const int* mask_class, const uint32_t* class_masks, int mask_words,
                       hipStream_t st);
+int pa_score_workspace_floats(int rows, int V);
+int pa_score_tokens(float* out_lp, int* out_rank, int out_stride, int* top_ids, float* top_lp, int top_stride,
+                    float* workspace, const void* logits, int rows, int V, int ld, const int* target,
+                    const int* lp_n, hipStream_t st);
 int pa_apply_penalties(void* logits, int rows, int V, int ld, int* counts, int* distinct, int* n_distinct,
                        int slots, int cap, const int* pen_slot, const int* pen_reset, const float* presence,
                        const float* frequency, const int* forced, const int* pair_start, const int* pair_n,
@@ -722,6 +726,48 @@ void token_logprobs(at::Tensor out_lp, at::Tensor top_ids, at::Tensor top_lp, at
              "token_logprobs");
 }
 
+int64_t score_workspace_floats(int64_t rows, int64_t V) { return pa_score_workspace_floats(rows, V); }
+
+// Prompt scoring (scoring.hip): logprob, rank and top-20 of target[row] per logit row. out_lp /
+// out_rank [rows] with one common stride, top_ids / top_lp [rows, 20]: unit inner stride, any
+// row stride (columns of one record buffer). Rows with target < 0 are left untouched.
+void score_tokens(at::Tensor out_lp, at::Tensor out_rank, at::Tensor top_ids, at::Tensor top_lp,
+                  at::Tensor workspace, at::Tensor logits, at::Tensor target, at::Tensor lp_n) {
+  check_gpu(workspace, "workspace"); check_gpu(target, "target"); check_gpu(lp_n, "lp_n");
+  TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.stride(1) == 1,
+              "logits must be a 2-D GPU tensor with unit inner stride");
+  check_dtype(logits, at::kBFloat16, "logits"); check_dtype(workspace, at::kFloat, "workspace");
+  check_dtype(target, at::kInt, "target"); check_dtype(lp_n, at::kInt, "lp_n");
+  check_dtype(out_lp, at::kFloat, "out_lp"); check_dtype(out_rank, at::kInt, "out_rank");
+  check_dtype(top_ids, at::kInt, "top_ids"); check_dtype(top_lp, at::kFloat, "top_lp");
+  const int64_t rows = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(out_lp.is_cuda() && out_lp.dim() == 1 && out_lp.size(0) >= rows, "out_lp: [rows] GPU tensor");
+  TORCH_CHECK(out_rank.is_cuda() && out_rank.dim() == 1 && out_rank.size(0) >= rows &&
+                  (rows <= 1 || out_rank.stride(0) == out_lp.stride(0)),
+              "out_rank: [rows] GPU tensor laid out like out_lp");
+  TORCH_CHECK(top_ids.is_cuda() && top_ids.dim() == 2 && top_ids.size(0) >= rows && top_ids.size(1) == 20 &&
+                  top_ids.stride(1) == 1,
+              "top_ids: [rows, 20] GPU tensor with unit inner stride");
+  TORCH_CHECK(top_lp.is_cuda() && top_lp.dim() == 2 && top_lp.size(0) >= rows && top_lp.size(1) == 20 &&
+                  top_lp.stride(1) == 1 && top_lp.stride(0) == top_ids.stride(0),
+              "top_lp: [rows, 20] GPU tensor laid out like top_ids");
+  TORCH_CHECK(rows == 0 || (out_lp.stride(0) >= 1 && top_ids.stride(0) >= 20), "score outputs overlap");
+  TORCH_CHECK(target.numel() >= rows && lp_n.numel() >= rows, "per-row score parameter tensors too short");
+  TORCH_CHECK(target.is_contiguous() && lp_n.is_contiguous(), "target / lp_n must be contiguous");
+  const int64_t ld = rows > 1 ? logits.stride(0) : V;  // a one-row view's stride is arbitrary
+  TORCH_CHECK(V > 0 && V % 8 == 0 && ld % 8 == 0 && ld >= V, "logits: V and the row stride must be multiples of 8");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(logits.data_ptr()) & 15) == 0,
+              "logits must start 16-byte aligned (rows are read as 16-byte vectors)");
+  TORCH_CHECK(V <= 64 * 4096, "score_tokens supports vocabularies up to 262144 entries");
+  TORCH_CHECK(workspace.numel() >= pa_score_workspace_floats(rows, V), "score workspace too small");
+  TORCH_CHECK(workspace.is_contiguous(), "score workspace must be contiguous");
+  check_rc(pa_score_tokens(out_lp.data_ptr<float>(), out_rank.data_ptr<int>(), (int)out_lp.stride(0),
+                           top_ids.data_ptr<int>(), top_lp.data_ptr<float>(), (int)top_ids.stride(0),
+                           workspace.data_ptr<float>(), logits.data_ptr(), (int)rows, (int)V, (int)ld,
+                           target.data_ptr<int>(), lp_n.data_ptr<int>(), cur_stream()),
+           "score_tokens");
+}
+
 // Presence / frequency penalties on the logits of the penalised sampling rows (penalties.hip):
 // counts [slots, V], distinct [slots, cap], n_distinct [slots] are the per-slot device state.
 void apply_penalties(at::Tensor logits, at::Tensor counts, at::Tensor distinct, at::Tensor n_distinct,
@@ -1210,6 +1256,9 @@ PYBIND11_MODULE(_C, m) {
   m.def("token_logprobs", &token_logprobs, py::arg("out_lp"), py::arg("top_ids"), py::arg("top_lp"),
         py::arg("workspace"), py::arg("logits"), py::arg("tokens"), py::arg("lp_n"), py::arg("forced"),
         py::arg("mask_class"), py::arg("class_masks"));
+  m.def("score_workspace_floats", &score_workspace_floats);
+  m.def("score_tokens", &score_tokens, py::arg("out_lp"), py::arg("out_rank"), py::arg("top_ids"),
+        py::arg("top_lp"), py::arg("workspace"), py::arg("logits"), py::arg("target"), py::arg("lp_n"));
   m.def("apply_penalties", &apply_penalties, py::arg("logits"), py::arg("counts"), py::arg("distinct"),
         py::arg("n_distinct"), py::arg("pen_slot"), py::arg("pen_reset"), py::arg("presence"),
         py::arg("frequency"), py::arg("forced"), py::arg("pair_start"), py::arg("pair_n"), py::arg("pair_tok"));

@@ -47,6 +47,18 @@ py::list outputs_to_py(const std::vector<SeqOutput>& outs) {
       }
       lps = recs;
     }
+    // ... of a scoring request (it generates nothing, so it has no such records): per scored
+    // prompt token (logprob, rank, [(token id, logprob) x <= n])
+    if (o.score_from >= 0) {
+      py::list recs;
+      for (const ScoreRecord& r : o.score_records) {
+        py::list top;
+        for (int32_t i = 0; i < o.score_n && i < LOGPROB_TOP && r.ids[i] >= 0; ++i)
+          top.append(py::make_tuple(r.ids[i], (double)r.lps[i]));
+        recs.append(py::make_tuple((double)r.lp, r.rank, top));
+      }
+      lps = recs;
+    }
     l.append(py::make_tuple(o.id, o.tokens, o.finish_reason, o.prompt_len, o.cached_prompt_tokens,
                             o.num_sampled, o.num_forced, o.t_first_token, o.t_finish, o.embed_slot, lps));
   }
@@ -206,6 +218,7 @@ PYBIND11_MODULE(_runtime, m) {
         d["rep_slot"] = L.rep_slot; d["rep_reset"] = L.rep_reset; d["rep_r"] = L.rep_r;
         d["rep_inv_r"] = L.rep_inv_r; d["rep_start"] = L.rep_start; d["rep_n"] = L.rep_n;
         d["rep_tok"] = L.rep_tok; d["rep_cap"] = L.rep_cap; d["rep_total"] = L.rep_total;
+        d["score_target"] = L.score_target; d["score_total"] = L.score_total;
         d["total"] = L.total;
         return d;
       })
@@ -215,11 +228,12 @@ PYBIND11_MODULE(_runtime, m) {
               const std::vector<int32_t>& stop_ids, const py::object& grammar, int32_t top_k,
               float top_p, bool embed, bool embed_last, int32_t logprobs, float presence_penalty,
               float frequency_penalty, const std::vector<std::pair<int32_t, float>>& logit_bias,
-              float min_p, float ln_min_p, float repetition_penalty, float inv_repetition_penalty) {
+              float min_p, float ln_min_p, float repetition_penalty, float inv_repetition_penalty,
+              int32_t score_from) {
              s.add_request(id, prompt, temperature, max_tokens, seed, ignore_eos, stop_ids,
                            make_grammar(grammar), top_k, top_p, embed, embed_last, logprobs,
                            presence_penalty, frequency_penalty, logit_bias, min_p, ln_min_p,
-                           repetition_penalty, inv_repetition_penalty);
+                           repetition_penalty, inv_repetition_penalty, score_from);
            },
            py::arg("id"), py::arg("prompt"), py::arg("temperature"), py::arg("max_tokens"),
            py::arg("seed"), py::arg("ignore_eos"), py::arg("stop_ids"), py::arg("grammar"),
@@ -228,7 +242,7 @@ PYBIND11_MODULE(_runtime, m) {
            py::arg("frequency_penalty") = 0.0f,
            py::arg("logit_bias") = std::vector<std::pair<int32_t, float>>{}, py::arg("min_p") = 0.0f,
            py::arg("ln_min_p") = 0.0f, py::arg("repetition_penalty") = 1.0f,
-           py::arg("inv_repetition_penalty") = 0.0f)
+           py::arg("inv_repetition_penalty") = 0.0f, py::arg("score_from") = -1)
       // words: the buffer's size in 32-bit words (0 = not stated: steps of requests with a
       // repetition penalty, which write behind layout()["total"], are then refused)
       .def("schedule", [](Scheduler& s, uintptr_t buf, int32_t words) {
@@ -237,17 +251,24 @@ PYBIND11_MODULE(_runtime, m) {
       }, py::arg("buf"), py::arg("words") = 0)
       // logprobs: address of the step's LogprobRecord array (41 32-bit words per sampling row:
       // logprob, 20 ids, 20 logprobs), 0 = the step computed none
-      .def("commit", [](Scheduler& s, uintptr_t sampled, int32_t n, uintptr_t logprobs) {
+      // scores: address of the step's ScoreRecord array (42 words per row: logprob, rank, 20 ids,
+      // 20 logprobs; indexed by row like `sampled`), 0 = the step computed none
+      .def("commit", [](Scheduler& s, uintptr_t sampled, int32_t n, uintptr_t logprobs, uintptr_t scores) {
         std::vector<SeqOutput> outs;
         {
           py::gil_scoped_release nogil;
           outs = s.commit(reinterpret_cast<const int32_t*>(sampled), n,
-                          reinterpret_cast<const LogprobRecord*>(logprobs));
+                          reinterpret_cast<const LogprobRecord*>(logprobs),
+                          reinterpret_cast<const ScoreRecord*>(scores));
         }
         return outputs_to_py(outs);
-      }, py::arg("sampled"), py::arg("n"), py::arg("logprobs") = 0)
+      }, py::arg("sampled"), py::arg("n"), py::arg("logprobs") = 0, py::arg("scores") = 0)
       .def_property_readonly_static("LOGPROB_RECORD_WORDS",
                                     [](const py::object&) { return (int)(sizeof(LogprobRecord) / 4); })
+      .def_property_readonly_static("SCORE_RECORD_WORDS",
+                                    [](const py::object&) { return (int)(sizeof(ScoreRecord) / 4); })
+      .def_property_readonly_static("COUNTS9_SCORE_BIT", [](const py::object&) { return (int)COUNTS9_SCORE_BIT; })
+      .def_property_readonly_static("FINISH_SCORE", [](const py::object&) { return (int)FINISH_SCORE; })
       .def("abort", &Scheduler::abort)
       .def("take_embed_resets", &Scheduler::take_embed_resets)
       .def("num_free_embed_rows", &Scheduler::num_free_embed_rows)

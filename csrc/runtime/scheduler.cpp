@@ -92,6 +92,8 @@ Scheduler::Scheduler(const SchedulerConfig& cfg)
   L.rep_cap = L.max_tokens + cfg.max_model_len;
   L.rep_tok = take(L.rep_cap);
   L.rep_total = o;
+  L.score_target = take(L.max_seqs);
+  L.score_total = o;
   for (int32_t r = L.max_seqs; r-- > 0;) embed_free_.push_back(r);
   for (int32_t r = std::max(0, std::min(cfg.max_num_seqs, cfg.penalty_slots)); r-- > 0;) pen_free_.push_back(r);
 }
@@ -102,9 +104,29 @@ void Scheduler::add_request(int64_t id, std::vector<int32_t> prompt, float tempe
                             int32_t top_k, float top_p, bool embed, bool embed_last, int32_t logprobs,
                             float presence_penalty, float frequency_penalty,
                             std::vector<std::pair<int32_t, float>> logit_bias, float min_p,
-                            float ln_min_p, float repetition_penalty, float inv_repetition_penalty) {
+                            float ln_min_p, float repetition_penalty, float inv_repetition_penalty,
+                            int32_t score_from) {
+  if (score_from != -1) {
+    // nothing of a scoring request may be dropped or changed silently: its records are
+    // per prompt position
+    if (score_from < 1 || score_from > (int32_t)prompt.size() - 1)
+      throw std::invalid_argument("scheduler: score_from must lie in [1, prompt_len - 1]");
+    if ((int32_t)prompt.size() >= cfg_.max_model_len)
+      throw std::invalid_argument("scheduler: a scoring request's prompt must be shorter than max_model_len");
+    if (embed || grammar || presence_penalty != 0.f || frequency_penalty != 0.f || !logit_bias.empty() ||
+        min_p != 0.f || repetition_penalty != 1.f)
+      throw std::invalid_argument("scheduler: a scoring request takes no embed, grammar, penalty, "
+                                  "logit_bias, min_p or repetition_penalty");
+  }
   auto s = std::make_unique<Sequence>();
   s->id = id;
+  if (score_from != -1) {
+    s->score_from = score_from;
+    s->score_n = std::max(0, std::min(logprobs, LOGPROB_TOP));
+    logprobs = -1;  // no record per generated token: there are none
+    score_requested_ = true;
+    ++score_live_;
+  }
   if ((int32_t)prompt.size() >= cfg_.max_model_len)
     prompt.resize(cfg_.max_model_len - 1);  // keep room for at least one generated token
   if (prompt.empty()) prompt.push_back(0);
@@ -192,6 +214,7 @@ void Scheduler::preempt(Sequence* s) {
   // partial sums must be cleared before the next step runs (take_embed_resets)
   if (s->embed_slot >= 0) embed_resets_.push_back(s->embed_slot);
   free_seq(s, true);
+  s->score_records.clear();  // a scoring request starts over: its final output is that of one run
   s->num_computed = 0;
   s->running = false;
   s->preempted = true;
@@ -209,7 +232,9 @@ bool Scheduler::ensure_blocks(Sequence* s, int32_t upto_tokens) {
 void Scheduler::match_prefix(Sequence* s) {
   const int32_t B = cfg_.block_size;
   if (cfg_.prefix_caching && (!s->embed || s->embed_last)) {
-    const int32_t n_full = ((int32_t)s->tokens.size() - 1) / B;  // never reuse the last token
+    // never reuse the last token; a scoring request computes position score_from - 1 (its first
+    // logits row) itself, everything before it may come from the cache
+    const int32_t n_full = (s->scoring() ? s->score_from - 1 : (int32_t)s->tokens.size() - 1) / B;
     uint64_t parent = 0;
     for (int32_t b = 0; b < n_full; ++b) {
       const int32_t* t = s->tokens.data() + (size_t)b * B;
@@ -248,7 +273,39 @@ int32_t Scheduler::schedule(int32_t* buf, int32_t buf_words) {
   if (rep_requested_ && buf_words < L.rep_total)  // before anything is planned or written
     throw std::invalid_argument("scheduler: a request with a repetition penalty needs a step buffer of "
                                 "layout().rep_total words, stated as schedule()'s second argument");
+  if (score_requested_ && buf_words < L.score_total)
+    throw std::invalid_argument("scheduler: a scoring request needs a step buffer of "
+                                "layout().score_total words, stated as schedule()'s second argument");
   last_plan_.clear();
+  // rows of the step (sampling rows + scoring rows) never exceed max_num_seqs. A scoring request
+  // can own many: every running sequence that may sample keeps one in reserve, so decode rows are
+  // served first whatever the order, and a scoring chunk is cut to the rows that are left (it
+  // continues next step). Without scoring requests none of this binds: one row per sequence.
+  // The reserve is taken before the token budget is dealt out, so it is an upper bound: a
+  // sequence whose remaining tokens could fit this step counts even if the budget then runs out
+  // before it (a scoring chunk is cut a little harder than needed, never the other way round);
+  // one still more than a step's tokens away from its last prompt token cannot sample and does
+  // not count. All of it is skipped while no scoring request is alive (score_live_).
+  int32_t rows_reserved = 0, score_rows_used = 0;
+  const bool budget_rows = score_live_ > 0;
+  if (budget_rows)
+    for (const Sequence* r : running_)
+      if (r->running && !r->embed && !r->scoring() &&
+          (int32_t)r->tokens.size() - r->num_computed <= cfg_.max_num_batched_tokens)
+        ++rows_reserved;
+  // a scoring entry of n tokens from c0 owns the rows of its positions >= score_from - 1
+  auto score_rows_of = [](const Sequence* s, int32_t c0, int32_t n) {
+    return s->scoring() ? std::max(0, c0 + n - std::max(c0, s->score_from - 1)) : 0;
+  };
+  // cut n so that the entry's rows fit what is left; 0 = nothing fits this step
+  auto fit_score_rows = [&](const Sequence* s, int32_t n) {
+    const int32_t avail = std::max(0, cfg_.max_num_seqs - rows_reserved - score_rows_used);
+    const int32_t pre = std::max(0, s->score_from - 1 - s->num_computed);  // tokens before the first row
+    return std::min(n, pre + avail);
+  };
+  auto samples = [](const Sequence* s, int32_t n) {
+    return !s->embed && !s->scoring() && s->num_computed + n == (int32_t)s->tokens.size();
+  };
   int32_t tok_budget = cfg_.max_num_batched_tokens;
   int32_t prefill_budget = cfg_.max_prefill_tokens;
   // words of the pair region (penalties) the planned sampling rows will take: a penalised row
@@ -286,9 +343,10 @@ int32_t Scheduler::schedule(int32_t* buf, int32_t buf_words) {
       last_plan_.push_back(std::move(e));
       continue;
     }
-    const int32_t pending = (int32_t)s->tokens.size() - s->num_computed;
+    const int32_t pending = s->compute_len() - s->num_computed;
     if (pending <= 0 || tok_budget <= 0) continue;
-    const int32_t n = std::min(pending, tok_budget);
+    int32_t n = std::min(pending, tok_budget);
+    if (s->scoring() && (n = fit_score_rows(s, n)) <= 0) continue;  // no row left: next step
     const int32_t pairs = pair_need(s, n);
     if (pair_used + pairs > L.pair_cap) continue;  // its new tokens do not fit the pair region: next step
     const int32_t reps = rep_need(s, n);
@@ -312,10 +370,11 @@ int32_t Scheduler::schedule(int32_t* buf, int32_t buf_words) {
       if (s->inflight == 0) preempt(s);
       continue;
     }
-    last_plan_.push_back({s, n, !s->embed && s->num_computed + n == (int32_t)s->tokens.size()});
+    last_plan_.push_back({s, n, samples(s, n)});
     tok_budget -= n;
     pair_used += pairs;
     rep_used += reps;
+    score_rows_used += score_rows_of(s, s->num_computed, n);
   }
   running_.erase(std::remove_if(running_.begin(), running_.end(),
                                 [](Sequence* s) { return !s->running; }),
@@ -371,9 +430,19 @@ int32_t Scheduler::schedule(int32_t* buf, int32_t buf_words) {
       deferred.push_back(s);
       continue;
     }
+    // with scoring requests about, a request that will sample needs a row that no scoring chunk
+    // of this step took (never binding otherwise: one row per planned sequence)
+    if (budget_rows && !s->embed && !s->scoring() &&
+        rows_reserved + score_rows_used >= cfg_.max_num_seqs)
+      break;
     if (s->blocks.empty()) match_prefix(s);
-    const int32_t pending = (int32_t)s->tokens.size() - s->num_computed;
-    const int32_t n = std::min(pending, std::min(tok_budget, prefill_budget));
+    const int32_t pending = s->compute_len() - s->num_computed;
+    int32_t n = std::min(pending, std::min(tok_budget, prefill_budget));
+    if (s->scoring() && (n = fit_score_rows(s, n)) <= 0) {  // no row left: the requests behind it may fit
+      waiting_.pop_front();
+      deferred.push_back(s);
+      continue;
+    }
     const int32_t pairs = pair_need(s, n);
     const int32_t reps = rep_need(s, n);
     // never with an empty step: one backlog always fits either region
@@ -399,7 +468,9 @@ int32_t Scheduler::schedule(int32_t* buf, int32_t buf_words) {
     s->preempted = false;
     running_.push_back(s);
     if (key && s->num_computed < 2 * B) inflight.insert(key);  // its leading blocks are computed now
-    last_plan_.push_back({s, n, !s->embed && s->num_computed + n == (int32_t)s->tokens.size()});
+    last_plan_.push_back({s, n, samples(s, n)});
+    score_rows_used += score_rows_of(s, s->num_computed, n);
+    if (budget_rows && samples(s, n)) ++rows_reserved;
     tok_budget -= n;
     prefill_budget -= n;
   }
@@ -422,7 +493,7 @@ int32_t Scheduler::schedule(int32_t* buf, int32_t buf_words) {
           const int32_t cut = std::min(left, p.n - 1);
           p.n -= cut;
           left -= cut;
-          p.sample = !p.s->embed && p.s->num_computed + p.n == (int32_t)p.s->tokens.size();
+          p.sample = samples(p.s, p.n);
         }
         ++stat_aligned_steps_;
       }
@@ -490,6 +561,13 @@ int32_t Scheduler::schedule(int32_t* buf, int32_t buf_words) {
   int32_t* rnn = buf + L.rep_n;
   int32_t* rtk = buf + L.rep_tok;
   int32_t nrep = 0, nreptok = 0;
+  // prompt scoring: the target region is written only when a planned entry owns scoring rows
+  bool any_score = false;
+  for (Planned& p : last_plan_) {
+    p.score_rows = score_rows_of(p.s, p.s->num_computed, p.n);
+    any_score = any_score || p.score_rows > 0;
+  }
+  int32_t* stg = buf + L.score_target;
   const int32_t tpw = 16 / std::max(1, cfg_.gqa_group);
 
   int32_t T = 0, ns = 0, nsamp = 0, nit = 0, nparted = 0, pslot = 0;
@@ -624,6 +702,7 @@ int32_t Scheduler::schedule(int32_t* buf, int32_t buf_words) {
       seeds[nsamp] = s->seed;
       lpn[nsamp] = s->logprobs;
       if (s->logprobs >= 0) ++nlp;
+      if (any_score) stg[nsamp] = -1;
       if (any_pen) {
         psl[nsamp] = -1;
         prs[nsamp] = 0;
@@ -688,6 +767,45 @@ int32_t Scheduler::schedule(int32_t* buf, int32_t buf_words) {
           bvl[nbias + j] = s->logit_bias[j].second;
         }
         nbias += nb;
+      }
+      ++nsamp;
+    }
+    // scoring rows: one per position >= score_from - 1 of the entry, each on that token's logit
+    // row with the next prompt token as its target. For every other pass the row is inert: forced
+    // to the target (the sampler emits it, the penalty / shaping / logprob passes skip it or write
+    // a record nobody reads), greedy, no mask class, no slot, no bias.
+    for (int32_t j = n - p.score_rows; j < n; ++j) {
+      if (nsamp >= L.max_seqs)  // the planning above budgeted the rows
+        throw std::logic_error("scheduler: scoring rows overflow max_num_seqs");
+      const int32_t target = s->tokens[c0 + j + 1];
+      lr[nsamp] = T + j;
+      mc[nsamp] = -1;
+      fc[nsamp] = target;
+      off[nsamp] = c0 + j + 1;
+      temp[nsamp] = 0.f;
+      tk[nsamp] = 0;
+      tp[nsamp] = 1.f;
+      seeds[nsamp] = 0;
+      lpn[nsamp] = s->score_n;
+      stg[nsamp] = target;
+      if (any_pen) {
+        psl[nsamp] = -1;
+        prs[nsamp] = 0;
+        ppr[nsamp] = pfr[nsamp] = 0.f;
+        pst[nsamp] = npair;
+        pnn[nsamp] = 0;
+      }
+      if (any_rep) {
+        rsl[nsamp] = -1;
+        rrs[nsamp] = 0;
+        rrr[nsamp] = rir[nsamp] = 1.f;
+        rst[nsamp] = nreptok;
+        rnn[nsamp] = 0;
+      }
+      if (any_shape) {
+        bst[nsamp] = nbias;
+        bnn[nsamp] = 0;
+        bmp[nsamp] = bln[nsamp] = 0.f;
       }
       ++nsamp;
     }
@@ -787,6 +905,8 @@ int32_t Scheduler::schedule(int32_t* buf, int32_t buf_words) {
       bnn[r] = 0;
       bmp[r] = bln[r] = 0.f;
     }
+  if (any_score)
+    for (int32_t r = nsamp; r < L.max_seqs; ++r) stg[r] = -1;
   for (int32_t r = ns; r < L.max_seqs; ++r) {
     qs[r] = T;
     ql[r] = 0;
@@ -804,6 +924,7 @@ int32_t Scheduler::schedule(int32_t* buf, int32_t buf_words) {
   counts[9] = npen > 0 ? 1 : 0;  // the step has a penalised sampling row (penalty pass)
   // ... a row with a repetition penalty (repetition pass): bit 1, the rep_tok words in use above it
   if (nrep > 0) counts[9] |= 2 | (nreptok << 2);
+  if (any_score) counts[9] |= COUNTS9_SCORE_BIT;  // ... scoring rows (scoring pass): bit 30
   counts[10] = npair;            // words of the pair region those rows use
   counts[11] = any_shape ? 1 + nbias : 0;  // a shaped sampling row (logit_bias / min_p pass) + its bias words
   if (nit > L.max_items)  // by construction (psz guard above, max_items sizing) this cannot happen
@@ -863,6 +984,11 @@ SeqOutput Scheduler::finish(Sequence* s, int32_t reason, double now) {
   o.logprobs = s->logprobs;
   o.lp_records = std::move(s->lp_records);
   s->lp_records.clear();
+  if (s->scoring()) --score_live_;
+  o.score_from = s->score_from;
+  o.score_n = s->score_n;
+  o.score_records = std::move(s->score_records);
+  s->score_records.clear();
   if (s->pen_slot >= 0) {  // recycled by the next holder's reset flag
     pen_free_.push_back(s->pen_slot);
     s->pen_slot = -1;
@@ -872,7 +998,8 @@ SeqOutput Scheduler::finish(Sequence* s, int32_t reason, double now) {
   return o;
 }
 
-std::vector<SeqOutput> Scheduler::commit(const int32_t* sampled, int32_t n, const LogprobRecord* lp) {
+std::vector<SeqOutput> Scheduler::commit(const int32_t* sampled, int32_t n, const LogprobRecord* lp,
+                                         const ScoreRecord* sc) {
   std::vector<SeqOutput> outs;
   if (plans_.empty()) return outs;
   Plan plan = std::move(plans_.front());
@@ -885,6 +1012,34 @@ std::vector<SeqOutput> Scheduler::commit(const int32_t* sampled, int32_t n, cons
   for (const Planned& p : plan.rows) {
     Sequence* s = p.s;
     int32_t tok = -1;
+    if (s->scoring()) {
+      // the entry's rows hold its records; their sampled tokens (the forced targets) are ignored
+      if (idx + p.score_rows > n) break;
+      const int32_t first = idx;
+      idx += p.score_rows;
+      if (s->done || s->abort_pending) continue;
+      for (int32_t j = 0; j < p.score_rows; ++j) {
+        if (sc) {
+          s->score_records.push_back(sc[first + j]);
+        } else {  // the step computed no records: keep the alignment with the positions
+          ScoreRecord r;
+          r.lp = NAN;
+          r.rank = 0;
+          for (int32_t i = 0; i < LOGPROB_TOP; ++i) {
+            r.ids[i] = -1;
+            r.lps[i] = -INFINITY;
+          }
+          s->score_records.push_back(r);
+        }
+      }
+      if (p.score_rows > 0 && s->t_first_token < 0) s->t_first_token = now;
+      register_full_blocks(s);
+      if (p.end == s->compute_len()) {
+        outs.push_back(finish(s, FINISH_SCORE, now));
+        done.push_back(s);
+      }
+      continue;
+    }
     if (p.sample) {
       if (idx >= n) break;
       tok = sampled[idx++];

@@ -126,13 +126,22 @@ struct StepLayout {
   int32_t rep_tok;    // [rep_cap]
   int32_t rep_cap;    // max_tokens + max_model_len: one whole backlog always fits
   int32_t rep_total;
+  // prompt scoring (csrc/ops/scoring.hip), behind rep_total: written and copied only by steps
+  // with a scoring row, which set bit 30 of counts[9]. rep_total and everything before it keep
+  // their values; score_total is the whole buffer, and schedule() refuses a scoring request
+  // unless the buffer is stated to be that long.
+  int32_t score_target;  // [max_seqs]: the token each row scores (tokens[p + 1]), -1 = not a scoring row
+  int32_t score_total;
 };
+
+constexpr int32_t COUNTS9_SCORE_BIT = 1 << 30;  // counts[9]: the step has scoring rows
 
 constexpr int32_t LOGIT_BIAS_MAX = 300;  // entries of one request's logit_bias
 
 enum FinishReason : int32_t {
   NOT_FINISHED = -1, FINISH_STOP = 0, FINISH_LENGTH = 1, FINISH_ABORT = 2,
-  FINISH_EMBED = 3  // embedding request: prompt fully prefilled, pooled hidden state ready
+  FINISH_EMBED = 3,  // embedding request: prompt fully prefilled, pooled hidden state ready
+  FINISH_SCORE = 4   // scoring request: the last scored prompt position has its record
 };
 
 // Log-probability record of one generated token, as the device writes it per sampling row
@@ -145,6 +154,17 @@ struct LogprobRecord {
   float lps[LOGPROB_TOP];
 };
 static_assert(sizeof(LogprobRecord) == 4 * (1 + 2 * LOGPROB_TOP), "LogprobRecord is 41 packed 32-bit words");
+
+// Record of one scored prompt token, as the device writes it per scoring row (csrc/ops/scoring.hip
+// score_merge_kernel): the token's logprob, its rank in the vocabulary (1 = most likely; larger
+// logit first, equal logits by smaller id), then the alternatives as in LogprobRecord.
+struct ScoreRecord {
+  float lp;
+  int32_t rank;
+  int32_t ids[LOGPROB_TOP];
+  float lps[LOGPROB_TOP];
+};
+static_assert(sizeof(ScoreRecord) == 4 * (2 + 2 * LOGPROB_TOP), "ScoreRecord is 42 packed 32-bit words");
 
 struct SeqOutput {
   int64_t id;
@@ -159,6 +179,9 @@ struct SeqOutput {
   int32_t embed_slot = -1;  // pooling row of an embedding request (FINISH_EMBED: holds the sums)
   int32_t logprobs = -1;    // alternatives the request asked for (-1: it did not ask)
   std::vector<LogprobRecord> lp_records;  // logprobs >= 0: one per entry of `tokens`
+  int32_t score_from = -1;  // scoring request: the first scored prompt position (-1: not one)
+  int32_t score_n = 0;      // ... and the alternatives it asked for
+  std::vector<ScoreRecord> score_records;  // FINISH_SCORE: prompt_len - score_from entries
 };
 
 struct Sequence {
@@ -207,6 +230,15 @@ struct Sequence {
   bool rep_fresh = false;
   bool repetitive() const { return !embed && repetition_penalty != 1.f; }
   bool needs_slot() const { return penalised() || repetitive(); }
+  // scoring request (score_from = k >= 1): generates nothing. Positions k-1 .. len-2 are computed,
+  // each with one row of the step whose target is the next prompt token; the last prompt token
+  // predicts nothing and is not computed. score_records: one per scored position so far.
+  int32_t score_from = -1;
+  int32_t score_n = 0;
+  std::vector<ScoreRecord> score_records;
+  bool scoring() const { return score_from >= 0; }
+  // tokens whose KV / logits the request still needs: all of them, or all but a scoring request's last
+  int32_t compute_len() const { return (int32_t)tokens.size() - (scoring() ? 1 : 0); }
   bool ignore_eos = false;
   std::vector<int32_t> stop_ids;
   int64_t arrival = 0;
@@ -244,7 +276,11 @@ class Scheduler {
                    float presence_penalty = 0.f, float frequency_penalty = 0.f,
                    std::vector<std::pair<int32_t, float>> logit_bias = {}, float min_p = 0.f,
                    float ln_min_p = 0.f, float repetition_penalty = 1.f,
-                   float inv_repetition_penalty = 0.f);  // 0: float32(1 / r) is computed here
+                   float inv_repetition_penalty = 0.f,  // 0: float32(1 / r) is computed here
+                   // k in [1, prompt_len - 1]: a scoring request over prompt positions k .. len-1
+                   // (`logprobs` = its alternatives, 0..20; nothing is generated; grammar, penalties,
+                   // logit_bias, min_p and embed are not allowed); anything else but -1 throws
+                   int32_t score_from = -1);
   bool abort(int64_t id);
   // Fill `buf` (layout()) for the next step. Returns the number of tokens in the
   // step (0 = nothing to run).
@@ -265,11 +301,16 @@ class Scheduler {
   // buffer). Once a request with a repetition penalty has been added, schedule() throws
   // std::invalid_argument unless buf_words >= layout().rep_total, so a caller that sized its buffer by `total` and then adds a
   // request with a repetition penalty gets an error, never a write past its buffer.
+  // The same holds one region further for scoring requests: once one has been added, schedule()
+  // throws unless buf_words >= layout().score_total.
   int32_t schedule(int32_t* buf, int32_t buf_words = 0);
   // Consume the sampled tokens of the oldest uncommitted step (one per sampling row).
   // `lp`: the step's log-probability records, one per sampling row (nullptr: the step computed
   // none); rows of requests that did not ask hold nothing meaningful and are not read.
-  std::vector<SeqOutput> commit(const int32_t* sampled, int32_t n, const LogprobRecord* lp = nullptr);
+  // `sc`: the step's score records, indexed by row like `sampled` (a scoring row counts as one of
+  // the n rows; its sampled token is ignored); nullptr: the step computed none.
+  std::vector<SeqOutput> commit(const int32_t* sampled, int32_t n, const LogprobRecord* lp = nullptr,
+                                const ScoreRecord* sc = nullptr);
   int32_t inflight_steps() const { return (int32_t)plans_.size(); }
   int64_t spec_rows() const { return stat_spec_rows_; }
   int64_t spec_voided() const { return stat_spec_voided_; }
@@ -319,6 +360,7 @@ class Scheduler {
     int32_t n;
     bool sample;
     int32_t end = 0;              // num_computed after this entry (its last token's position + 1)
+    int32_t score_rows = 0;       // scoring request: rows of the step this entry owns (its last tokens)
     bool spec = false;            // speculative continuation of a row sampling in the previous plan
     bool voided = false;          // the speculation failed: nothing of this entry is committed
     int32_t src_idx = -1;         // spec: sampling row of the pending token in the previous plan
@@ -341,6 +383,8 @@ class Scheduler {
   std::vector<int32_t> embed_resets_;  // rows of preempted embedding requests, to be cleared
   std::vector<int32_t> pen_free_;      // free penalty slots
   bool rep_requested_ = false;         // a request with a repetition penalty was added: see schedule()
+  bool score_requested_ = false;       // a scoring request was added: see schedule() (the buffer's size)
+  int32_t score_live_ = 0;             // scoring requests not yet finished: the row budget applies
   int64_t arrival_counter_ = 0;
   int64_t stat_prompt_tokens_ = 0, stat_cached_tokens_ = 0, stat_preemptions_ = 0, stat_steps_ = 0;
   int64_t stat_aligned_steps_ = 0;

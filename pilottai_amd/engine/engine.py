@@ -178,6 +178,11 @@ class GenerationOutput:
     # of softmax(logits) over the allowed tokens at temperature 1; grammar-forced tokens have 0.0
     logprobs: Optional[List[Tuple[float, List[Tuple[int, float]]]]] = field(default=None, repr=False)
     cumulative_logprob: Optional[float] = None  # sum of the tokens' logprobs (None: not asked)
+    # submit(score_from=k): per prompt position k .. len-1 (logprob of the prompt's token there given
+    # the tokens before it, its rank in the vocabulary -- 1 = most likely --, [(token id, logprob)] of
+    # the <= n most likely tokens); natural log of softmax(logits) over the whole vocabulary at
+    # temperature 1. finish_reason is "score", token_ids is empty, cumulative_logprob their sum
+    prompt_logprobs: Optional[List[Tuple[float, int, List[Tuple[int, float]]]]] = field(default=None, repr=False)
 
     @property
     def text(self) -> str:
@@ -192,7 +197,7 @@ class GenerationOutput:
         return max(0.0, self.t_finish - self.t_arrival)
 
 
-_REASONS = {0: "stop", 1: "length", 2: "abort", 3: "embed"}
+_REASONS = {0: "stop", 1: "length", 2: "abort", 3: "embed", 4: "score"}
 
 
 @dataclass
@@ -219,6 +224,7 @@ class _Request:
     ln_min_p: float = 0.0           # float32(ln min_p), computed once here for host and device
     repetition_penalty: float = 1.0      # 1 off; else in (0, 2]
     inv_repetition_penalty: float = 1.0  # float32(1 / r), computed once here for host and device
+    score_from: int = -1                 # -1 off; k: a scoring request over prompt positions k .. len-1
 
 
 class LLMEngine:
@@ -325,11 +331,11 @@ class LLMEngine:
         # one being scheduled); the device copy is stream-ordered behind the previous step
         self._async = bool(cfg.async_steps) and self.tp.size == 1
         nbuf = 2 if self._async else 1
-        self._host_metas = [torch.zeros(L["rep_total"], dtype=torch.int32, pin_memory=pin) for _ in range(nbuf)]
+        self._host_metas = [torch.zeros(L["score_total"], dtype=torch.int32, pin_memory=pin) for _ in range(nbuf)]
         self._host_meta = self._host_metas[0]
         self._host_ptr = self._host_meta.data_ptr()
         self._host_np = self._host_meta.numpy()
-        self._dev_meta = torch.zeros(L["rep_total"], dtype=torch.int32, device=self.device) \
+        self._dev_meta = torch.zeros(L["score_total"], dtype=torch.int32, device=self.device) \
             if (self.on_gpu or self._async) else self._host_meta
         # attention tickets: one per (sequence, KV head) for split decode rows, then -- only with
         # prefill_split_keys on -- one per (partial slot, KV head) for split prefill items
@@ -388,6 +394,20 @@ class LLMEngine:
         self._lp_hosts = [torch.zeros(S, W, dtype=torch.int32, pin_memory=pin) for _ in range(nbuf)]
         self._lp_ws = ops.token_logprobs_workspace(S, self.model.v_local, self.device) \
             if (self.on_gpu and self.tp.size == 1) else None
+        # prompt scoring (submit(score_from=k)): one 42-word record per scoring row (logprob, rank,
+        # 20 ids, 20 logprobs: the scheduler's ScoreRecord), written by ops.score_tokens behind the
+        # sampler in the step graph's scoring variant and copied to the host with the sampled
+        # tokens. TP > 1 is refused at submit().
+        W2 = self._rt.Scheduler.SCORE_RECORD_WORDS
+        assert W2 == 2 + 2 * ops.LOGPROB_TOP
+        self._sc_rec = torch.zeros(S, W2, dtype=torch.int32, device=self.device)
+        scf = self._sc_rec.view(torch.float32)
+        self._sc_out = (scf[:, 0], self._sc_rec[:, 1], self._sc_rec[:, 2:2 + ops.LOGPROB_TOP],
+                        scf[:, 2 + ops.LOGPROB_TOP:])
+        self._sc_hosts = [torch.zeros(S, W2, dtype=torch.int32, pin_memory=pin) for _ in range(nbuf)]
+        self._sc_ws = ops.score_tokens_workspace(S, self.model.v_local, self.device) \
+            if (self.on_gpu and self.tp.size == 1) else None
+        self._score_bit = int(self._rt.Scheduler.COUNTS9_SCORE_BIT)
         # presence / frequency penalties (submit(presence_penalty=, frequency_penalty=)): per-slot
         # token counts on the device, allocated on the first penalised request; ops.apply_penalties
         # rewrites the logits behind the LM head in the step graph's penalty variant
@@ -403,7 +423,8 @@ class LLMEngine:
         # with the log-probability pass has the 4-tuple key (bucket, trunc, embed, True), a step
         # with a penalised row the 5-tuple key (bucket, trunc, embed, lp, True), a step with a
         # logit_bias / min_p row the 6-tuple key (bucket, trunc, embed, lp, pen, True), a step
-        # with a repetition-penalty row the 7-tuple key (bucket, trunc, embed, lp, pen, shape, True).
+        # with a repetition-penalty row the 7-tuple key (bucket, trunc, embed, lp, pen, shape, True),
+        # a step with scoring rows the 8-tuple key (bucket, trunc, embed, lp, pen, shape, rep, True).
         self._graphs: Dict[tuple, "torch.cuda.CUDAGraph"] = {}
         self._tau = torch.empty(S, dtype=torch.float32, device=self.device)
         self._graph_pool = None
@@ -512,6 +533,7 @@ class LLMEngine:
         self._rep_start = sl("rep_start", ms)
         self._rep_n = sl("rep_n", ms)
         self._rep_tok = sl("rep_tok", L["rep_cap"])
+        self._score_target = sl("score_target", ms)
 
     def _sync_masks(self) -> bool:
         reg = self.grammar.reg
@@ -545,7 +567,8 @@ class LLMEngine:
                                                    self.device)
 
     def _forward_and_sample(self, bucket: int, s_b: int, ns: int, trunc: bool = False, embed: bool = False,
-                            lp: bool = False, pen: bool = False, shape: bool = False, rep: bool = False):
+                            lp: bool = False, pen: bool = False, shape: bool = False, rep: bool = False,
+                            score: bool = False):
         meta = self._meta_for(bucket, s_b, ns)
         if self._async:  # pending tokens of rows that sampled in the previous step
             ops.patch_pending_ids(meta.input_ids[:bucket], self._sampled_dev)
@@ -607,10 +630,18 @@ class LLMEngine:
             ops.token_logprobs(logits, self._sampled_dev[:s_b], self._lp_n[:s_b], self._forced[:s_b],
                                self._mask_cls[:s_b], self._class_masks,
                                out=(o_lp[:s_b], o_ids[:s_b], o_lps[:s_b]), workspace=self._lp_ws)
+        if score:
+            # on the logits as every other pass of the step left them: scoring rows are forced, so
+            # no penalty / bias pass touched theirs, and no grammar mask applies
+            s_lp, s_rank, s_ids, s_lps = self._sc_out
+            ops.score_tokens(logits, self._score_target[:s_b], self._lp_n[:s_b],
+                             out=(s_lp[:s_b], s_rank[:s_b], s_ids[:s_b], s_lps[:s_b]), workspace=self._sc_ws)
 
     @staticmethod
     def _graph_key(bucket: int, trunc: bool, embed: bool, lp: bool = False, pen: bool = False,
-                   shape: bool = False, rep: bool = False) -> tuple:
+                   shape: bool = False, rep: bool = False, score: bool = False) -> tuple:
+        if score:
+            return (bucket, trunc, embed, lp, pen, shape, rep, True)
         if rep:
             return (bucket, trunc, embed, lp, pen, shape, True)
         if shape:
@@ -620,26 +651,27 @@ class LLMEngine:
         return (bucket, trunc, embed, True) if lp else (bucket, trunc, embed)
 
     def _run(self, bucket: int, ns: int, trunc: bool, n_copy: int, embed: bool = False, lp: bool = False,
-             pen: bool = False, shape: bool = False, rep: bool = False):
-        """Replay the (bucket, trunc, embed[, logprobs[, penalties[, shaping[, repetition]]]]) graph
+             pen: bool = False, shape: bool = False, rep: bool = False, score: bool = False):
+        """Replay the (bucket, trunc, embed[, logprobs[, penalties[, shaping[, repetition[, scoring]]]]]) graph
         — capturing it first if needed — or run eagerly."""
         if pen:
             self._ensure_pen_state()
         if rep:
             self._ensure_rep_state()
         if not self.use_graphs:
-            self._forward_and_sample(bucket, self._seq_bucket(bucket), ns, trunc, embed, lp, pen, shape, rep)
+            self._forward_and_sample(bucket, self._seq_bucket(bucket), ns, trunc, embed, lp, pen, shape, rep,
+                                     score)
             return
-        key = self._graph_key(bucket, trunc, embed, lp, pen, shape, rep)
+        key = self._graph_key(bucket, trunc, embed, lp, pen, shape, rep, score)
         g = self._graphs.get(key)
         if g is None:
-            if shape or rep:  # their regions lie behind the copied prefix: keep the whole buffer
-                n_copy = self.L["rep_total"]
+            if shape or rep or score:  # their regions lie behind the copied prefix: keep the whole buffer
+                n_copy = self.L["score_total"]
             saved = self._dev_meta[:n_copy].clone()
             pool = self._embed_pool.clone()
             samp = self._sampled_dev.clone()  # the previous step's tokens (pipelined mode)
             self.capture_graphs([bucket], trunc=trunc, embed=embed, lp=lp, pen=pen,
-                                shape=shape, rep=rep)  # clobbers the device metadata
+                                shape=shape, rep=rep, score=score)  # clobbers the device metadata
             self.stats["graph_captures"] += 1  # a first-use capture inside serving (tens of ms)
             self._dev_meta[:n_copy].copy_(saved)
             self._embed_pool.copy_(pool)
@@ -658,6 +690,11 @@ class LLMEngine:
             a = L["bias_val"]
             self._dev_meta[a:a + n_bias].copy_(hm[a:a + n_bias], non_blocking=self.on_gpu)
 
+    def _copy_scoring(self, hm: torch.Tensor):
+        """Host -> device copy of the scoring region of a step with scoring rows (the per-row targets)."""
+        a, b = self.L["score_target"], self.L["score_target"] + self.L["max_seqs"]
+        self._dev_meta[a:b].copy_(hm[a:b], non_blocking=self.on_gpu)
+
     def _copy_repetition(self, hm: torch.Tensor, n_tok: int):
         """Host -> device copy of the repetition regions of a step with such a row: the per-row
         words and the `n_tok` token words in use, one piece."""
@@ -670,12 +707,13 @@ class LLMEngine:
     def _dummy_meta(self):
         """A metadata state under which a forward touches no KV and no attention item."""
         L = self.L
-        d = torch.zeros(L["rep_total"], dtype=torch.int32)
+        d = torch.zeros(L["score_total"], dtype=torch.int32)
         d[L["slots"]:L["slots"] + L["max_tokens"]] = -1
         d[L["embed_rows"]:L["embed_rows"] + L["max_tokens"]] = L["max_seqs"]
         d[L["pen_slot"]:L["pen_slot"] + L["max_seqs"]] = -1  # the penalty pass touches nothing
         # bias_n = 0 and min_p = 0 (the zeros above): the logit_bias / min_p passes touch nothing
         d[L["rep_slot"]:L["rep_slot"] + L["max_seqs"]] = -1  # the repetition pass touches nothing
+        d[L["score_target"]:L["score_target"] + L["max_seqs"]] = -1  # the scoring pass touches nothing
         self._dev_meta.copy_(d.to(self.device))
 
     def capture_embed_graphs(self):
@@ -686,10 +724,12 @@ class LLMEngine:
         self.capture_graphs(embed=True)
 
     def capture_graphs(self, buckets: Optional[Sequence[int]] = None, trunc: bool = False, embed: bool = False,
-                       lp: bool = False, pen: bool = False, shape: bool = False, rep: bool = False):
+                       lp: bool = False, pen: bool = False, shape: bool = False, rep: bool = False,
+                       score: bool = False):
         """Capture one hipGraph per token bucket (shared memory pool); the top-k/top-p,
-        embedding-pooling, log-probability, penalty, logit_bias / min_p (`shape`) and repetition
-        penalty (`rep`) variants are captured on first use, or up front by a call with the flag set."""
+        embedding-pooling, log-probability, penalty, logit_bias / min_p (`shape`), repetition
+        penalty (`rep`) and prompt-scoring (`score`) variants are captured on first use, or up front
+        by a call with the flag set."""
         if not self.use_graphs:
             return
         if pen:
@@ -701,7 +741,7 @@ class LLMEngine:
             self._graph_pool = torch.cuda.graph_pool_handle()
         t0 = time.time()
         for b in sorted(buckets or self.buckets, reverse=True):
-            key = self._graph_key(b, trunc, embed, lp, pen, shape, rep)
+            key = self._graph_key(b, trunc, embed, lp, pen, shape, rep, score)
             if key in self._graphs:
                 continue
             s_b = self._seq_bucket(b)
@@ -709,11 +749,11 @@ class LLMEngine:
             st.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(st):
                 for _ in range(2):
-                    self._forward_and_sample(b, s_b, 0, trunc, embed, lp, pen, shape, rep)
+                    self._forward_and_sample(b, s_b, 0, trunc, embed, lp, pen, shape, rep, score)
             torch.cuda.current_stream().wait_stream(st)
             g = torch.cuda.CUDAGraph(keep_graph=True) if self.cfg.keep_graphs else torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, pool=self._graph_pool):
-                self._forward_and_sample(b, s_b, 0, trunc, embed, lp, pen, shape, rep)
+                self._forward_and_sample(b, s_b, 0, trunc, embed, lp, pen, shape, rep, score)
             if self.cfg.keep_graphs:
                 g.instantiate()
             self._graphs[key] = g
@@ -771,7 +811,7 @@ class LLMEngine:
                request_id: Optional[int] = None, top_k: int = 0, top_p: float = 1.0,
                embed: Union[bool, str] = False, logprobs: int = -1, presence_penalty: float = 0.0,
                frequency_penalty: float = 0.0, logit_bias: Optional[Mapping[int, float]] = None,
-               min_p: float = 0.0, repetition_penalty: float = 1.0) -> int:
+               min_p: float = 0.0, repetition_penalty: float = 1.0, score_from: Optional[int] = None) -> int:
         """Thread-safe; `callback` runs on the engine thread when the request finishes.
 
         top_k > 0 / top_p < 1 truncate the (grammar-masked) distribution before
@@ -813,9 +853,25 @@ class LLMEngine:
         not touched. Greedy rows are penalised, logprobs are those of the penalised distribution.
         The request holds a penalty slot (shared with its additive penalties); its tokens do not
         depend on what it is batched with and survive preemption. Not for embedding requests, not
-        on a TP > 1 engine, not with async_steps."""
+        on a TP > 1 engine, not with async_steps.
+
+        score_from = k, 1 <= k <= len(prompt_ids) - 1: a scoring request. Nothing is generated;
+        for every prompt position p in [k, len) the output's prompt_logprobs carries the
+        log-probability of prompt_ids[p] given the tokens before it (softmax over the whole
+        vocabulary at temperature 1, no grammar mask), its rank in the vocabulary (1 = most likely;
+        larger logit first, equal logits by smaller id, on the bf16 logits) and the `logprobs` = n
+        (0..20, default 0) most likely tokens there. finish_reason is "score", token_ids is empty,
+        cumulative_logprob the sum. Positions before k - 1 may come from the prefix cache and the
+        request's blocks are cached like any other's, so K candidates over one context pay for the
+        context once. temperature, top_k, top_p, seed and max_tokens are ignored; embed, a grammar,
+        any penalty, logit_bias, min_p and repetition_penalty are refused, as is a TP > 1 engine."""
         if self._err is not None:
             raise RuntimeError(f"engine failed: {self._err!r}")
+        if score_from is not None:
+            return self._submit_score(prompt_ids, callback, score_from, logprobs, request_id,
+                                      dict(embed=embed, grammar=grammar, presence_penalty=presence_penalty,
+                                           frequency_penalty=frequency_penalty, logit_bias=logit_bias,
+                                           min_p=min_p, repetition_penalty=repetition_penalty))
         logprobs = -1 if logprobs is None else int(logprobs)
         if not -1 <= logprobs <= ops.LOGPROB_TOP:
             raise ValueError(f"logprobs must be -1 (off) or 0..{ops.LOGPROB_TOP}, not {logprobs}")
@@ -866,6 +922,77 @@ class LLMEngine:
         self._inbox.put(req)
         self._wake.set()
         return rid
+
+    def _submit_score(self, prompt_ids, callback, score_from, logprobs, request_id, others) -> int:
+        """submit(score_from=k): validate and queue a scoring request."""
+        ids = list(prompt_ids)
+        k = score_from
+        if isinstance(k, bool) or not isinstance(k, Integral) or not 1 <= k <= len(ids) - 1:
+            raise ValueError(f"score_from must be an integer in [1, len(prompt_ids) - 1], not {k!r}")
+        V = self.model_cfg.vocab_size
+        for t in ids:
+            if isinstance(t, bool) or not isinstance(t, Integral) or not 0 <= t < V:
+                raise ValueError(f"scoring request: token id {t!r} is not an integer in [0, {V})")
+        if len(ids) >= self.max_model_len:
+            raise ValueError(f"scoring request: {len(ids)} tokens do not fit max_model_len {self.max_model_len}")
+        n = 0 if logprobs is None or int(logprobs) == -1 else int(logprobs)
+        if not 0 <= n <= ops.LOGPROB_TOP:
+            raise ValueError(f"logprobs must be 0..{ops.LOGPROB_TOP} on a scoring request, not {logprobs}")
+        if others["embed"]:
+            raise ValueError("a scoring request cannot be an embedding request")
+        if others["grammar"] is not None:
+            raise ValueError("scoring under a grammar is not supported")
+        for name, off in (("presence_penalty", 0.0), ("frequency_penalty", 0.0), ("min_p", 0.0),
+                          ("repetition_penalty", 1.0)):
+            v = others[name]
+            if v is not None and v != off:
+                raise ValueError(f"{name} is not available on a scoring request")
+        if others["logit_bias"]:
+            raise ValueError("logit_bias is not available on a scoring request")
+        if self.tp.size > 1:
+            raise ValueError("scoring is not supported on a tensor-parallel (TP > 1) engine")
+        rid = request_id if request_id is not None else self.new_request_id()
+        req = _Request(rid, [int(t) for t in ids], 0.0, 1, 0, True, [], None, callback, self._rt.now(),
+                       logprobs=n, score_from=int(k))
+        self._inbox.put(req)
+        self._wake.set()
+        return rid
+
+    def score(self, context_ids: Sequence[int], candidates_ids: Sequence[Sequence[int]],
+              top: int = 0) -> List[GenerationOutput]:
+        """Score each candidate continuation of one context: one scoring request per candidate,
+        context + candidate with score_from = len(context), so output i carries the logprob, rank
+        and `top` alternatives of every token of candidate i (prompt_logprobs) and their sum
+        (cumulative_logprob). The requests share the context's KV through the prefix cache.
+        Blocking; thread-safe; drives the loop inline if no engine thread is running."""
+        ctx = list(context_ids)
+        if not ctx:
+            raise ValueError("score() needs a non-empty context (the first token has nothing to condition on)")
+        cands = [list(c) for c in candidates_ids]
+        if any(not c for c in cands):
+            raise ValueError("score() needs non-empty candidates")
+        if not cands:
+            return []
+        results: Dict[int, GenerationOutput] = {}
+        done = threading.Event()
+        lock = threading.Lock()
+
+        def cb(o: GenerationOutput):
+            with lock:
+                results[o.request_id] = o
+                if len(results) == len(cands):
+                    done.set()
+
+        rids = [self.submit(ctx + c, cb, score_from=len(ctx), logprobs=top) for c in cands]
+        if self._thread is None:
+            while not done.is_set():
+                if not self.step() and not self.sched.has_work() and self._inbox.empty():
+                    break
+        else:
+            done.wait()
+        if self._err is not None:
+            raise RuntimeError(f"engine failed: {self._err!r}")
+        return [results[i] for i in rids]
 
     def add_step_listener(self, fn: Callable[[int], None]):
         """fn(tokens) runs on the engine thread right after each step is launched (keep it cheap:
@@ -1096,7 +1223,7 @@ class LLMEngine:
                                    req.ignore_eos, req.stop_ids, req.grammar, req.top_k, req.top_p, req.embed,
                                    req.embed_last, req.logprobs, req.presence_penalty, req.frequency_penalty,
                                    list(req.logit_bias), req.min_p, req.ln_min_p, req.repetition_penalty,
-                                   req.inv_repetition_penalty)
+                                   req.inv_repetition_penalty, req.score_from)
             self.stats["requests"] += 1
         while True:
             try:
@@ -1127,8 +1254,11 @@ class LLMEngine:
         out = GenerationOutput(rid, list(toks), _REASONS.get(reason, "stop"), plen, cached, len(toks),
                                nsamp, nforced, req.t_arrival, t_first, t_fin, self.tok, emb,
                                lps, None if lps is None else float(sum(e[0] for e in lps)))
+        if req.score_from >= 0:  # a scoring request's records are per prompt position: (logprob, rank, top)
+            out.logprobs, out.prompt_logprobs = None, lps
         # per-request timings: TTFT = arrival -> first token, TPOT = later tokens' mean gap
-        if t_first > 0:
+        # (generation only: a scoring request has no first token and no token gaps)
+        if t_first > 0 and req.score_from < 0:
             n_out = max(1, len(toks))
             self.timings.append((out.ttft, (t_fin - t_first) / max(1, n_out - 1), n_out))
         try:
@@ -1157,7 +1287,8 @@ class LLMEngine:
         c = self._host_np[L["counts"]:L["counts"] + 12]
         ns, nsamp, trunc, embed, lp = int(c[1]), int(c[2]), int(c[6]) > 0, int(c[7]) > 0, int(c[8]) > 0
         pen = (int(c[9]) & 1) > 0
-        rep = int(c[9]) >> 1  # 0, or 1 + 2 * the token words of the step's repetition-penalty rows
+        score = (int(c[9]) & self._score_bit) > 0  # the step has scoring rows
+        rep = (int(c[9]) & (self._score_bit - 1)) >> 1  # 0, or 1 + 2 * the token words of the step's repetition-penalty rows
         shape = int(c[11])  # 0, or 1 + the bias words of the step's logit_bias / min_p rows
         bucket = next(b for b in self.buckets if b >= T)
         s_b = self._seq_bucket(bucket)
@@ -1174,19 +1305,23 @@ class LLMEngine:
                 self._copy_shaping(self._host_meta, shape - 1)
             if rep:
                 self._copy_repetition(self._host_meta, rep >> 1)
+            if score:
+                self._copy_scoring(self._host_meta)
         if self.tp.size > 1:
             self._tp_send(_OP_STEP, T, ns, nsamp, bucket, int(masks_changed), n_copy, int(trunc), int(embed))
             if masks_changed:
                 self.tp.broadcast(self._class_masks)
             self.tp.broadcast(self._dev_meta[:n_copy])
         with torch.inference_mode(), trace_range("engine.forward"):
-            self._run(bucket, ns, trunc, n_copy, embed, lp, pen, shape > 0, rep > 0)
+            self._run(bucket, ns, trunc, n_copy, embed, lp, pen, shape > 0, rep > 0, score)
         if self._step_listeners:
             self._notify_launch(T)
         if nsamp:
             self._sampled_host[:nsamp].copy_(self._sampled_dev[:nsamp], non_blocking=self.on_gpu)
         if lp:
             self._lp_hosts[0][:nsamp].copy_(self._lp_rec[:nsamp], non_blocking=self.on_gpu)
+        if score:
+            self._sc_hosts[0][:nsamp].copy_(self._sc_rec[:nsamp], non_blocking=self.on_gpu)
         self._health_fetch()
         t_launch = time.perf_counter()
         # the previous step's finished requests are handed to their callers while this step
@@ -1199,7 +1334,8 @@ class LLMEngine:
         t_sync = time.perf_counter()
         with trace_range("engine.commit"):
             outs = self.sched.commit(self._sampled_host.data_ptr(), nsamp,
-                                     self._lp_hosts[0].data_ptr() if lp else 0)
+                                     self._lp_hosts[0].data_ptr() if lp else 0,
+                                     self._sc_hosts[0].data_ptr() if score else 0)
         if embed:
             self._read_embeddings(outs)
         st = self.stats
@@ -1256,6 +1392,7 @@ class LLMEngine:
         c = hm.numpy()[L["counts"]:L["counts"] + 12]
         ns, nsamp, trunc, embed, lp = int(c[1]), int(c[2]), int(c[6]) > 0, int(c[7]) > 0, int(c[8]) > 0
         shape = int(c[11])  # 0, or 1 + the bias words of the step's logit_bias / min_p rows
+        score = (int(c[9]) & self._score_bit) > 0  # the step has scoring rows
         bucket = next(b for b in self.buckets if b >= T)
         self._sync_masks()
         n_copy = L["embed_rows"] + bucket if embed else L["block_table"] + ns * L["max_blocks"]
@@ -1265,14 +1402,18 @@ class LLMEngine:
         self._dev_meta[:n_copy].copy_(hm[:n_copy], non_blocking=self.on_gpu)
         if shape:
             self._copy_shaping(hm, shape - 1)
+        if score:
+            self._copy_scoring(hm)
         with torch.inference_mode(), trace_range("engine.forward"):
-            self._run(bucket, ns, trunc, n_copy, embed, lp, shape=shape > 0)
+            self._run(bucket, ns, trunc, n_copy, embed, lp, shape=shape > 0, score=score)
         if self._step_listeners:
             self._notify_launch(T)
         if nsamp:
             self._sampled_hosts[slot][:nsamp].copy_(self._sampled_dev[:nsamp], non_blocking=self.on_gpu)
         if lp:
             self._lp_hosts[slot][:nsamp].copy_(self._lp_rec[:nsamp], non_blocking=self.on_gpu)
+        if score:
+            self._sc_hosts[slot][:nsamp].copy_(self._sc_rec[:nsamp], non_blocking=self.on_gpu)
         if embed:
             self._embed_hosts[slot].copy_(self._embed_pool, non_blocking=self.on_gpu)
         self._health_fetch()
@@ -1281,7 +1422,7 @@ class LLMEngine:
             ev = torch.cuda.Event()
             ev.record()
         t_launch = time.perf_counter()
-        self._inflight.append((slot, T, bucket, nsamp, embed, ev, t0, lp))
+        self._inflight.append((slot, T, bucket, nsamp, embed, ev, t0, lp, score))
         self._slot = (slot + 1) % len(self._host_metas)
         st = self.stats
         st["host_sched_s"] += t_sched - t0
@@ -1291,7 +1432,7 @@ class LLMEngine:
         return True
 
     def _complete(self, rec):
-        slot, T, bucket, nsamp, embed, ev, t0, lp = rec
+        slot, T, bucket, nsamp, embed, ev, t0, lp, score = rec
         t_w = time.perf_counter()
         if ev is not None:
             ev.synchronize()
@@ -1299,7 +1440,8 @@ class LLMEngine:
         t_sync = time.perf_counter()
         with trace_range("engine.commit"):
             outs = self.sched.commit(self._sampled_hosts[slot].data_ptr(), nsamp,
-                                     self._lp_hosts[slot].data_ptr() if lp else 0)
+                                     self._lp_hosts[slot].data_ptr() if lp else 0,
+                                     self._sc_hosts[slot].data_ptr() if score else 0)
         if embed:
             self._read_embeddings(outs, self._embed_hosts[slot])
         st = self.stats

@@ -18,6 +18,7 @@ the same names) are sent under their OpenAI names when non-zero. `response_forma
 ({token id: bias}) is sent in the OpenAI wire form (keys as strings), `response_format["min_p"]`
 (default `LLMConfig.min_p`) as `min_p` when non-zero, `response_format["repetition_penalty"]`
 (default `LLMConfig.repetition_penalty`) as `repetition_penalty` when it is not 1.
+`score()` / `choose()` call `POST /v1/score` when the server is a pilottai one.
 
     LLMConfig(provider="openai", base_url="http://10.0.0.5:8000/v1", api_key=...)
 """
@@ -45,6 +46,8 @@ class OpenAICompatLLM(BaseLLM):
         self._headers = {"Authorization": f"Bearer {key}"} if key else {}
         self.timeout_s = float(_cfg_get(config, "timeout", timeout_s) or timeout_s)
         self.schema_mode = schema_mode
+        # score() / choose() go to POST /v1/score, which only a pilottai_amd server has
+        self.supports_scoring = schema_mode == "pilottai"
         self._client = None
 
     def _http(self):
@@ -106,6 +109,32 @@ class OpenAICompatLLM(BaseLLM):
                 "tool_calls": msg.get("tool_calls"), "model": data.get("model", self.model_name),
                 "logprobs": (ch.get("logprobs") or {}).get("content"),
                 "usage": {"prompt_tokens": pt, "completion_tokens": ct, "total_tokens": pt + ct}}
+
+    async def score(self, messages_or_text, candidates, top: int = 0) -> List[Dict[str, Any]]:
+        """POST /v1/score of a pilottai_amd server (schema_mode "pilottai"); other OpenAI-compatible
+        servers have no such endpoint, so this raises NotImplementedError for them."""
+        if not self.supports_scoring:
+            return await super().score(messages_or_text, candidates, top)
+        ctx = messages_or_text if isinstance(messages_or_text, str) else list(messages_or_text)
+        r = await self._http().post(f"{self.base_url}/score", json={"context": ctx, "candidates": list(candidates),
+                                                                    "top_logprobs": int(top)})
+        if r.status_code == 404:
+            raise NotImplementedError(f"the server at {self.base_url} has no /score endpoint")
+        if r.status_code == 400:
+            raise ValueError(f"HTTP 400: {r.text[:300]}")
+        if r.status_code != 200:
+            raise RuntimeError(f"HTTP {r.status_code}: {r.text[:300]}")
+        data = r.json()
+        inf = lambda v: float("-inf") if v == -9999.0 else float(v)  # noqa: E731 -- the wire form of -inf
+        out = []
+        for s in sorted(data["scores"], key=lambda s: s["index"]):
+            toks = [dict(t, logprob=inf(t["logprob"]),
+                         top_logprobs=[dict(a, logprob=inf(a["logprob"])) for a in t.get("top_logprobs", [])])
+                    for t in s["tokens"]]
+            out.append({"logprob": inf(s["logprob"]), "tokens": toks})
+        self.usage["calls"] += 1
+        self.usage["prompt_tokens"] += int((data.get("usage") or {}).get("prompt_tokens", 0))
+        return out
 
     async def list_models(self) -> List[str]:
         r = await self._http().get(f"{self.base_url}/models")

@@ -115,6 +115,26 @@ class BaseLLM:
     # response_format["logit_bias"] ({token id: bias}) / ["min_p"] are honoured
     supports_logit_shaping = False
     supports_repetition_penalty = False  # response_format["repetition_penalty"] is honoured
+    supports_scoring = False  # score() / choose(): log-probabilities of given candidate texts
+
+    async def score(self, messages_or_text: Union[str, Sequence[Dict[str, str]]], candidates: Sequence[str],
+                    top: int = 0) -> List[Dict[str, Any]]:
+        """Log-probability of each candidate text as the continuation of the context (a chat as
+        messages, or plain text): one {"logprob": sum, "tokens": [{token, token_id, logprob, rank,
+        bytes, top_logprobs}]} per candidate. Backends without a model to ask refuse."""
+        raise NotImplementedError(f"the {self.provider!r} LLM backend cannot score text "
+                                  "(supports_scoring is False): use the local engine or a pilottai_amd server")
+
+    async def choose(self, messages_or_text: Union[str, Sequence[Dict[str, str]]], options: Sequence[str],
+                     normalize: bool = False):
+        """Pick one of `options` by scoring them instead of decoding: returns (index, logprobs)
+        with the index of the largest summed logprob (or the largest mean per token when
+        `normalize` is set) and every option's figure."""
+        if not options:
+            raise ValueError("choose() needs at least one option")
+        res = await self.score(messages_or_text, list(options))
+        vals = [r["logprob"] / max(1, len(r["tokens"])) if normalize else r["logprob"] for r in res]
+        return max(range(len(vals)), key=lambda i: vals[i]), vals
 
     def __init__(self, config: Any = None):
         self.config = config
@@ -205,6 +225,7 @@ class LocalLLM(BaseLLM):
     supports_penalties = True
     supports_logit_shaping = True
     supports_repetition_penalty = True
+    supports_scoring = True
     prefix_cache_layout = True  # agents put the shared task text first (core/agent.py)
 
     def __init__(self, config: Any = None, engine=None):
@@ -220,6 +241,64 @@ class LocalLLM(BaseLLM):
         self.tok: Tokenizer = engine.tok
         if engine._thread is None:
             engine.start()
+
+    def context_ids(self, messages_or_text) -> List[int]:
+        """Token ids of a scoring context: a chat in the reply layout (the candidate is the
+        assistant's text), or plain text behind the begin-of-text token."""
+        if isinstance(messages_or_text, str):
+            return [BOS_ID] + self.tok.encode(messages_or_text)
+        messages = list(messages_or_text)
+        if not messages:
+            raise ValueError("Messages cannot be empty")
+        if self.shared_context:
+            messages = [{"role": "system", "content": self.shared_context}] + messages
+        return encode_chat(self.tok, messages)
+
+    async def score(self, messages_or_text, candidates: Sequence[str], top: int = 0) -> List[Dict[str, Any]]:
+        """One scoring request per candidate in the local continuous batch (engine.submit(score_from=)).
+        The context and each candidate are tokenised separately and concatenated, which fixes the
+        boundary; the candidates share the context's KV through the prefix cache."""
+        return (await self.score_usage(messages_or_text, candidates, top))[0]
+
+    async def score_usage(self, messages_or_text, candidates: Sequence[str], top: int = 0):
+        """score() plus what it cost: (results, {"prompt_tokens", "cached_prompt_tokens"}) summed
+        over the candidates' requests (the HTTP server's `usage`)."""
+        if isinstance(candidates, str) or not all(isinstance(c, str) for c in candidates):
+            raise ValueError("candidates must be a list of strings")
+        top = int(top)
+        if not 0 <= top <= 20:
+            raise ValueError(f"top must be 0..20, not {top}")
+        ctx = self.context_ids(messages_or_text)
+        cands = [self.tok.encode(c) for c in candidates]
+        if any(not c for c in cands):
+            raise ValueError("every candidate must hold at least one token")
+        loop = asyncio.get_running_loop()
+        futs, rids = [], []
+        try:
+            for c in cands:
+                fut = loop.create_future()
+                futs.append(fut)
+                rids.append(self.engine.submit(
+                    ctx + c, lambda out, fut=fut: loop.call_soon_threadsafe(lambda: fut.done() or fut.set_result(out)),
+                    score_from=len(ctx), logprobs=top))
+            outs = await asyncio.gather(*futs)
+        except asyncio.CancelledError:
+            for rid in rids:
+                self.engine.abort(rid)
+            raise
+        res = []
+        for c, out in zip(cands, outs):
+            if out.finish_reason != "score" or out.prompt_logprobs is None or len(out.prompt_logprobs) != len(c):
+                raise RuntimeError(f"scoring request did not complete: {out.finish_reason}")
+            toks = logprob_entries(self.tok, c, [(lp, alt) for lp, _, alt in out.prompt_logprobs])
+            for e, (_, rank, _) in zip(toks, out.prompt_logprobs):
+                e["rank"] = int(rank)
+            res.append({"logprob": float(out.cumulative_logprob), "tokens": toks})
+        usage = {"prompt_tokens": sum(o.prompt_tokens for o in outs),
+                 "cached_prompt_tokens": sum(o.cached_prompt_tokens for o in outs)}
+        self.usage["calls"] += 1
+        self.usage["prompt_tokens"] += usage["prompt_tokens"]
+        return res, usage
 
     async def _complete(self, messages, response_format, tools) -> Dict[str, Any]:
         grammar = None

@@ -241,6 +241,46 @@ def token_logprobs(logits, tokens, lp_n, forced, mask_class, class_masks, out=No
     return out
 
 
+SCORE_TOKENS_LAUNCHES = 2  # kernels score_tokens() launches on the GPU (chunk pass + row merge)
+
+
+def score_tokens_workspace(rows: int, V: int, device) -> torch.Tensor:
+    n = require_native().score_workspace_floats(rows, V)
+    return torch.empty(n, dtype=torch.float32, device=device)
+
+
+def score_tokens(logits, target, lp_n, out=None, workspace: Optional[torch.Tensor] = None):
+    """Prompt scoring (csrc/ops/scoring.hip): per row with target[row] >= 0, the natural-log
+    probability of that token under softmax(logits) over the whole vocabulary at temperature 1,
+    its rank (1 + the tokens with a larger logit or an equal logit and a smaller id, compared on
+    the bf16 order key, so exact) and the lp_n[row] (0..20) most likely tokens. Returns / fills
+    `out` = (logprob fp32 [rows], rank int32 [rows], top_ids int32 [rows, 20], top_lp fp32
+    [rows, 20]); the lists are those of token_logprobs (id -1 / -inf past the end). Rows with
+    target < 0 are left untouched; a target >= V gives (-inf, rank 0). The outputs may be strided
+    columns of one record buffer."""
+    rows = logits.shape[0]
+    if out is None:
+        out = (torch.empty(rows, dtype=torch.float32, device=logits.device),
+               torch.empty(rows, dtype=torch.int32, device=logits.device),
+               torch.empty(rows, LOGPROB_TOP, dtype=torch.int32, device=logits.device),
+               torch.empty(rows, LOGPROB_TOP, dtype=torch.float32, device=logits.device))
+    lp, rank, ids, lps = out
+    if _on_gpu(logits):
+        C = require_native()
+        if workspace is None:
+            workspace = score_tokens_workspace(rows, logits.shape[1], logits.device)
+        C.score_tokens(lp, rank, ids, lps, workspace, logits, target, lp_n)
+        return out
+    r_lp, r_rank, r_ids, r_lps = ref.score_tokens(logits, target, lp_n)
+    asked = (target[:rows] >= 0).cpu()
+    if bool(asked.any()):
+        lp[:rows][asked] = r_lp[asked]
+        rank[:rows][asked] = r_rank[asked]
+        ids[:rows][asked] = r_ids[asked]
+        lps[:rows][asked] = r_lps[asked]
+    return out
+
+
 PENALTY_LAUNCHES = 1  # kernels apply_penalties() launches on the GPU
 
 

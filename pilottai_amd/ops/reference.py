@@ -273,6 +273,52 @@ def token_logprobs(logits: torch.Tensor, tokens, lp_n, forced, mask_class, class
     return out_lp, out_ids, out_lps
 
 
+def bf16_order_keys(logits: torch.Tensor) -> np.ndarray:
+    """The 16-bit order key of every logit's bf16 value (int64 array): monotone in the value,
+    -0 below +0 (csrc/ops/logprob_common.h bf16_order_key)."""
+    b = logits.detach().cpu().to(torch.bfloat16).contiguous().view(torch.int16).numpy().astype(np.int64) & 0xFFFF
+    return np.where(b & 0x8000, ~b & 0xFFFF, b | 0x8000)
+
+
+def score_tokens(logits: torch.Tensor, target, lp_n, top: int = 20):
+    """Prompt scoring (fp64 math): per row with target t >= 0, log softmax(logits)[t] over the
+    whole vocabulary at temperature 1, the rank of t by the integer rule
+        1 + #{ i : key(x[i]) > key(x[t]) or (key(x[i]) == key(x[t]) and i < t) }
+    on the bf16 order key, and the min(lp_n, top) most likely tokens in that order.
+
+    Returns (logprob fp32 [rows], rank int32 [rows], top_ids int32 [rows, top], top_lp fp32
+    [rows, top]). Rows with target < 0 keep NaN / -1 / -1 / NaN (skipped). A target >= V gives
+    (-inf, rank 0); a logit of -inf gives -inf and is never listed; lists end with id -1 / -inf."""
+    rows, V = logits.shape
+    out_lp = torch.full((rows,), float("nan"), dtype=torch.float32)
+    out_rank = torch.full((rows,), -1, dtype=torch.int32)
+    out_ids = torch.full((rows, top), -1, dtype=torch.int32)
+    out_lps = torch.full((rows, top), float("nan"), dtype=torch.float32)
+    lg = logits.detach().cpu().to(torch.bfloat16).float().numpy().astype(np.float64)
+    keys = bf16_order_keys(logits)
+    idx = np.arange(V)
+    for r in range(rows):
+        t = int(target[r])
+        if t < 0:
+            continue
+        n = min(max(int(lp_n[r]), 0), top)
+        out_lps[r] = float("-inf")
+        x, k = lg[r], keys[r]
+        out_rank[r] = 1 + int(((k > k[t]) | ((k == k[t]) & (idx < t))).sum()) if t < V else 0
+        mx = x.max()
+        if not mx > -np.inf:
+            out_lp[r] = float("-inf")
+            continue
+        lse = mx + np.log(np.exp(x - mx).sum())
+        out_lp[r] = float(x[t] - lse) if t < V else float("-inf")
+        if n > 0:
+            order = np.argsort(-k, kind="stable")[:n]  # stable: equal keys keep ascending ids
+            order = order[x[order] > -np.inf]
+            out_ids[r, :order.size] = torch.from_numpy(order.astype(np.int32))
+            out_lps[r, :order.size] = torch.from_numpy((x[order] - lse).astype(np.float32))
+    return out_lp, out_rank, out_ids, out_lps
+
+
 def apply_penalties(logits: torch.Tensor, state, pen_slot, pen_reset, presence, frequency, forced,
                     pair_start, pair_n, pair_tok):
     """Presence / frequency penalties in place on `logits` [rows, V] (see ops.apply_penalties),

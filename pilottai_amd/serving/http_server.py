@@ -9,6 +9,12 @@ speak:
     GET  /health               liveness + engine metrics (steps, tokens/s, KV use, HBM)
     GET  /v1/models            the served model
     POST /v1/chat/completions  messages -> one completion (stream=true: SSE, one delta + [DONE])
+    POST /v1/score             {"context": str | messages, "candidates": [str, ...], "top_logprobs": 0..20}
+                               -> {"object": "score", "model", "scores": [{"index", "logprob", "tokens":
+                               [{token, token_id, logprob, rank, bytes, top_logprobs}]}], "usage"}: the
+                               log-probability of each candidate as the continuation of the context
+                               (nothing is generated; the candidates share the context's KV). -inf is
+                               sent as -9999.0; malformed bodies and the model-free backend answer 400
 
 `response_format` accepts the OpenAI forms and one extension:
 * {"type": "json_schema", "json_schema": {"name": ..., "schema": {...}}}: a JSON Schema
@@ -326,6 +332,43 @@ def create_app(llm, model_name: Optional[str] = None, engine=None) -> FastAPI:
             yield "data: [DONE]\n\n"
 
         return StreamingResponse(sse(), media_type="text/event-stream")
+
+    @app.post("/v1/score")
+    async def score(body: Dict[str, Any]):
+        ctx, cands, top = body.get("context"), body.get("candidates"), body.get("top_logprobs", 0)
+        if isinstance(ctx, str):
+            ok = len(ctx) > 0
+        else:
+            ok = isinstance(ctx, list) and len(ctx) > 0 and all(isinstance(m, dict) for m in ctx)
+        if not ok:
+            raise HTTPException(400, "context must be a non-empty string or a non-empty list of messages")
+        if not isinstance(cands, list) or not cands or not all(isinstance(c, str) and c for c in cands):
+            raise HTTPException(400, "candidates must be a non-empty list of non-empty strings")
+        if isinstance(top, bool) or not isinstance(top, int) or not 0 <= top <= 20:
+            raise HTTPException(400, "top_logprobs must be an integer between 0 and 20")
+        if not getattr(llm, "supports_scoring", False):
+            raise HTTPException(400, f"the {getattr(llm, 'provider', 'configured')} backend cannot score text")
+        try:
+            if hasattr(llm, "score_usage"):  # a backend that also reports what the call cost
+                res, used = await llm.score_usage(ctx, cands, top=top)
+            else:
+                res, used = await llm.score(ctx, cands, top=top), {}
+        except ValueError as e:
+            raise HTTPException(400, str(e))
+        except Exception as e:  # noqa: BLE001
+            raise HTTPException(500, f"scoring failed: {e}")
+        lp = lambda v: -9999.0 if v == float("-inf") or v != v else float(v)  # noqa: E731
+        scores = []
+        for i, r in enumerate(res):
+            wire = _wire_logprobs(r["tokens"])["content"]
+            for w, e in zip(wire, r["tokens"]):
+                w["rank"] = e["rank"]
+            scores.append({"index": i, "logprob": lp(r["logprob"]), "tokens": wire})
+        pt = int(used.get("prompt_tokens", 0))
+        return {"id": "score-" + uuid.uuid4().hex[:24], "object": "score", "created": int(time.time()),
+                "model": name, "scores": scores,
+                "usage": {"prompt_tokens": pt, "completion_tokens": 0, "total_tokens": pt,
+                          "cached_prompt_tokens": int(used.get("cached_prompt_tokens", 0))}}
 
     return app
 
