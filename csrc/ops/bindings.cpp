@@ -101,6 +101,11 @@ int pa_cosine_topk(float* out_scores, int* out_rows, void* workspace, const void
                    const void* index, int Q, int N, int D, int K, const int* row_priority,
                    const uint64_t* row_tags, const float* row_expiry, const int* q_min_priority,
                    const uint64_t* q_tags, float now, int n_valid, hipStream_t st);
+int pa_mmr_select_bf16(float* out_scores, int* out_rows, const int* rows, const float* scores, const void* packed,
+                       const float* wr, const float* wd, int Q, int m, int K, int D, int nrows, hipStream_t st);
+int pa_mmr_select_q16(float* out_scores, int* out_rows, const int* rows, const float* scores, const void* hi,
+                      const void* lo, const float* rmeta, const float* wr, const float* wd, int Q, int m, int K,
+                      int D, int nrows, hipStream_t st);
 long long pa_q16_topk_workspace_bytes(int Q, int N);
 int pa_q16_topk(float* out_scores, int* out_rows, int* unsafe, void* workspace, const void* queries_q,
                 const float* qmeta, const void* hi, const void* lo, const float* rmeta, int Q, int N, int D, int K,
@@ -991,6 +996,56 @@ void q16_topk(at::Tensor out_scores, at::Tensor out_rows, at::Tensor unsafe, at:
            "q16_topk");
 }
 
+// MMR re-ranking of a scan's candidate lists (csrc/ops/similarity_mmr.hip). `planes`: the bf16
+// index's packed tiles, or the q16 index's hi / lo planes with rmeta.
+void mmr_check_lists(const at::Tensor& out_scores, const at::Tensor& out_rows, const at::Tensor& rows,
+                     const at::Tensor& scores, const at::Tensor& wr, const at::Tensor& wd, int64_t K) {
+  check_dtype(out_scores, at::kFloat, "out_scores"); check_dtype(out_rows, at::kInt, "out_rows");
+  check_dtype(rows, at::kInt, "rows"); check_dtype(scores, at::kFloat, "scores");
+  check_dtype(wr, at::kFloat, "wr"); check_dtype(wd, at::kFloat, "wd");
+  TORCH_CHECK(rows.dim() == 2 && scores.sizes() == rows.sizes(), "rows / scores must be [Q, m]");
+  TORCH_CHECK(rows.is_contiguous() && scores.is_contiguous() && out_scores.is_contiguous() &&
+                  out_rows.is_contiguous() && wr.is_contiguous() && wd.is_contiguous(),
+              "mmr_select tensors must be contiguous");
+  const int64_t Q = rows.size(0), m = rows.size(1);
+  TORCH_CHECK(m >= 1 && m <= 64 && K >= 1 && K <= 64, "mmr_select takes 1..64 candidates and picks per query");
+  TORCH_CHECK(wr.numel() >= Q && wd.numel() >= Q, "wr / wd must be [Q]");
+  TORCH_CHECK(out_scores.numel() >= Q * K && out_rows.numel() >= Q * K, "output too small");
+}
+
+void mmr_select_bf16(at::Tensor out_scores, at::Tensor out_rows, at::Tensor rows, at::Tensor scores,
+                     at::Tensor packed, at::Tensor wr, at::Tensor wd, int64_t K) {
+  for (auto* t : {&out_scores, &out_rows, &rows, &scores, &packed, &wr, &wd}) check_gpu(*t, "mmr_select_bf16 arg");
+  mmr_check_lists(out_scores, out_rows, rows, scores, wr, wd, K);
+  check_dtype(packed, at::kBFloat16, "packed");
+  TORCH_CHECK(packed.dim() == 4 && packed.size(2) == 64 && packed.size(3) == 8 && packed.is_contiguous(),
+              "packed must be bf16 tiles [N/16, D/32, 64, 8] (memory/semantic_index.py)");
+  check_rc(pa_mmr_select_bf16(out_scores.data_ptr<float>(), out_rows.data_ptr<int>(), rows.data_ptr<int>(),
+                              scores.data_ptr<float>(), packed.data_ptr(), wr.data_ptr<float>(),
+                              wd.data_ptr<float>(), (int)rows.size(0), (int)rows.size(1), (int)K,
+                              (int)(packed.size(1) * 32), (int)(packed.size(0) * 16), cur_stream()),
+           "mmr_select_bf16");
+}
+
+void mmr_select_q16(at::Tensor out_scores, at::Tensor out_rows, at::Tensor rows, at::Tensor scores, at::Tensor hi,
+                    at::Tensor lo, at::Tensor rmeta, at::Tensor wr, at::Tensor wd, int64_t K) {
+  for (auto* t : {&out_scores, &out_rows, &rows, &scores, &hi, &lo, &rmeta, &wr, &wd})
+    check_gpu(*t, "mmr_select_q16 arg");
+  mmr_check_lists(out_scores, out_rows, rows, scores, wr, wd, K);
+  check_dtype(hi, at::kChar, "hi"); check_dtype(lo, at::kChar, "lo"); check_dtype(rmeta, at::kFloat, "rmeta");
+  TORCH_CHECK(hi.dim() == 4 && hi.size(2) == 64 && hi.size(3) == 16 && lo.sizes() == hi.sizes() &&
+                  hi.is_contiguous() && lo.is_contiguous(),
+              "hi / lo must be int8 planes [N/16, D/64, 64, 16] (memory/semantic_index.py storage='q16')");
+  TORCH_CHECK(rmeta.dim() == 2 && rmeta.size(1) == 2 && rmeta.is_contiguous(), "rmeta must be [N, 2]");
+  // a row id is followed only if both its tile and its scale exist
+  const int64_t nrows = std::min<int64_t>(hi.size(0) * 16, rmeta.size(0));
+  check_rc(pa_mmr_select_q16(out_scores.data_ptr<float>(), out_rows.data_ptr<int>(), rows.data_ptr<int>(),
+                             scores.data_ptr<float>(), hi.data_ptr(), lo.data_ptr(), rmeta.data_ptr<float>(),
+                             wr.data_ptr<float>(), wd.data_ptr<float>(), (int)rows.size(0), (int)rows.size(1), (int)K,
+                             (int)(hi.size(1) * 64), (int)nrows, cur_stream()),
+           "mmr_select_q16");
+}
+
 }  // namespace
 
 // One phase of the vocab-parallel top-k / top-p threshold (sampling.hip tp_topkp_kernel):
@@ -1275,6 +1330,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("cosine_topk", &cosine_topk);
   m.def("q16_topk_workspace_bytes", &q16_topk_workspace_bytes);
   m.def("q16_topk", &q16_topk);
+  m.def("mmr_select_bf16", &mmr_select_bf16);
+  m.def("mmr_select_q16", &mmr_select_q16);
   m.def("car_alloc", &car_alloc);
   m.def("car_open", &car_open);
   m.def("car_close", [](int64_t p) { return pa_car_close((void*)(uintptr_t)p); });

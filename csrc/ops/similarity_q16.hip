@@ -10,7 +10,7 @@
 // plus per row (s_r, b_r = s_r ||lo||_2). Queries are quantised the same way (v_q = 256 qh +
 // ql, scale s_q, c_q = s_q ||v_q||_2). The EXACT score of (row, query) is
 //     S = s_r s_q (v_q . v_r) = s_r s_q (65536 qh.hi + 256 (qh.lo + ql.hi) + ql.lo)
-// from four exact int32 dot products (exact_score below; the CPU reference in
+// from four exact int32 dot products (exact_score in q16_exact.h; the CPU reference in
 // ops/reference.py q16_topk evaluates the same int64 sum and the same float64 -> float32 step,
 // so GPU and reference agree bit for bit). 16-bit fixed point resolves each coordinate to
 // ~3e-6 -- finer than the bf16 index's 2^-9 relative.
@@ -35,6 +35,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "q16_exact.h"  // exact_score
 
 namespace pa {
 namespace q16 {
@@ -58,12 +59,6 @@ __host__ __device__ inline int num_wg(int N) {
   if (nwg > MAX_WG) nwg = MAX_WG;
   if (nwg < 1) nwg = 1;
   return nwg;
-}
-
-// the exact score (see the header); the ONLY place the integer sums become a float
-__device__ __forceinline__ float exact_score(int hh, int hl, int lh, int ll, float sr, float sq) {
-  const long long I = (long long)hh * 65536 + ((long long)hl + (long long)lh) * 256 + (long long)ll;
-  return (float)((double)I * ((double)sr * (double)sq));
 }
 
 // Bitonic sort of NC entries descending by key, carrying two payloads (whole block, >= NC threads).

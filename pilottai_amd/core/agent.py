@@ -96,7 +96,8 @@ class BaseAgent:
                  allow_delegation: Optional[bool] = None, tools: Optional[Sequence[Any]] = None,
                  step_callback: Optional[Callable] = None, *, agent_config: Optional[AgentConfig] = None,
                  llm_config: Optional[Union[LLMConfig, dict]] = None, policy: Optional[ControlPolicy] = None,
-                 memory: Any = None, memory_lookup: Any = None, memory_top_k: int = 3):
+                 memory: Any = None, memory_lookup: Any = None, memory_top_k: int = 3,
+                 memory_diversity: float = 0.0):
         # --- accept BaseAgent(agent_config, llm_config) and factory-style cls(config)
         if isinstance(role, AgentConfig):
             agent_config, role = role, None
@@ -154,6 +155,12 @@ class BaseAgent:
         # task + last result, and each finished task is written back
         self.memory_lookup = memory_lookup
         self.memory_top_k = int(memory_top_k)
+        # MMR diversity of every lookup, in [0, 1]: agents on related tasks fill the store with
+        # near-duplicates, and a plain top-k then spends the prompt's k hits on one memory
+        if isinstance(memory_diversity, bool) or not isinstance(memory_diversity, (int, float)) \
+                or not 0.0 <= memory_diversity <= 1.0:  # NaN fails both comparisons
+            raise ValueError(f"memory_diversity must be a finite number in [0, 1], not {memory_diversity!r}")
+        self.memory_diversity = float(memory_diversity)
         self.last_error: Optional[str] = None
         self.last_heartbeat = datetime.now()
         self._accepting = True
@@ -583,7 +590,11 @@ class BaseAgent:
         across all agents), as a short text block for the step-planning prompt."""
         query = f"{task.description[:400]} {last_result[:200]}"
         try:
-            hits = await self.memory_lookup.search(query, limit=self.memory_top_k)
+            if self.memory_diversity:
+                hits = await self.memory_lookup.search(query, limit=self.memory_top_k,
+                                                       diversity=self.memory_diversity)
+            else:
+                hits = await self.memory_lookup.search(query, limit=self.memory_top_k)
         except Exception as e:  # noqa: BLE001 — memory is advisory (reference: warn and go on)
             self.memory_errors["search"] += 1
             self.logger.warning("memory search failed: %s", e)

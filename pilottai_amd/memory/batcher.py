@@ -36,6 +36,7 @@ from collections import deque
 from typing import Any, Dict, List, Optional, Set, Tuple
 
 from .enhanced_memory import EnhancedMemory, MemoryItem
+from .semantic_index import check_diversity
 
 _log = logging.getLogger("pilottai.memory")
 
@@ -53,7 +54,8 @@ class MemoryLookupBatcher:
         self.min_batch = max(1, int(min_batch))
         self.max_wait_s = float(max_wait_s)
         self.time_device = time_device
-        self._pending: List[Tuple[str, Optional[Set[str]], int, int, "asyncio.Future", float]] = []
+        # (query, tags, min_priority, limit, future, enqueue time, diversity)
+        self._pending: List[Tuple[str, Optional[Set[str]], int, int, "asyncio.Future", float, float]] = []
         self._writes: List[Tuple[str, Dict[str, Any], Set[str], int, "asyncio.Future"]] = []
         self._flush_scheduled = False
         self._active = False  # a flush task is running (it drains everything pending)
@@ -136,9 +138,13 @@ class MemoryLookupBatcher:
 
     # ----------------------------------------------------------------- API
     async def search(self, query: str, limit: int = 5, tags: Optional[Set[str]] = None,
-                     min_priority: int = 0) -> List[MemoryItem]:
+                     min_priority: int = 0, diversity: float = 0.0) -> List[MemoryItem]:
+        """`diversity` in [0, 1]: MMR re-ranking of this lookup's hits (the store's search_batch);
+        lookups with different values share one pass, each keeping its own."""
+        check_diversity(diversity, 1)
         fut = asyncio.get_running_loop().create_future()
-        self._pending.append((query, tags, int(min_priority), int(limit), fut, time.perf_counter()))
+        self._pending.append((query, tags, int(min_priority), int(limit), fut, time.perf_counter(),
+                              float(diversity)))
         self._schedule()
         return await fut
 
@@ -231,8 +237,12 @@ class MemoryLookupBatcher:
                         self.stats["embed_s"] += time.perf_counter() - te
                     await self._await_heavy()
                 ts = time.perf_counter()
+                div = [b[6] for b in batch]
+                # the keyword only when a lookup asked for it: a plain batch calls the store as ever
+                extra = {"diversity": div} if any(div) else {}
                 hits = await self.memory.search_batch(qs, tags=[b[1] for b in batch],
-                                                      min_priority=[b[2] for b in batch], limit=limit, vecs=vecs)
+                                                      min_priority=[b[2] for b in batch], limit=limit, vecs=vecs,
+                                                      **extra)
                 self.stats["search_s"] += time.perf_counter() - ts
                 now = time.perf_counter()
                 for b, h in zip(batch, hits):

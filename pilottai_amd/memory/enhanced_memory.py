@@ -22,7 +22,7 @@ from typing import Any, Callable, Deque, Dict, List, Optional, Sequence, Set
 from pydantic import BaseModel, ConfigDict, Field
 
 from .embedding import HashingEmbedder
-from .semantic_index import SemanticIndex
+from .semantic_index import SemanticIndex, check_diversity, check_fetch_k
 
 
 class MemoryItem(BaseModel):
@@ -122,10 +122,14 @@ class EnhancedMemory:
         return rows
 
     async def semantic_search(self, query: str, tags: Optional[Set[str]] = None, min_priority: int = 0,
-                              limit: int = 5, mode: str = "semantic") -> List[MemoryItem]:
+                              limit: int = 5, mode: str = "semantic", diversity: float = 0.0,
+                              fetch_k: Optional[int] = None) -> List[MemoryItem]:
+        """`diversity` in [0, 1]: maximal-marginal-relevance re-ranking of the `fetch_k` best hits
+        (search_batch); 0 is the plain cosine top-`limit`."""
         if not query:
             raise ValueError("Query cannot be empty")
-        res = await self.search_batch([query], tags=[tags], min_priority=[min_priority], limit=limit, mode=mode)
+        res = await self.search_batch([query], tags=[tags], min_priority=[min_priority], limit=limit, mode=mode,
+                                      diversity=diversity, fetch_k=fetch_k)
         return res[0]
 
     async def embed_queries(self, queries: Sequence[str]):
@@ -137,17 +141,30 @@ class EnhancedMemory:
 
     async def search_batch(self, queries: Sequence[str], tags: Optional[Sequence[Optional[Set[str]]]] = None,
                            min_priority: Optional[Sequence[int]] = None, limit: int = 5,
-                           mode: str = "semantic", vecs=None) -> List[List[MemoryItem]]:
-        """`vecs`: the queries' embeddings from embed_queries (skips embedding here)."""
+                           mode: str = "semantic", vecs=None, diversity=0.0,
+                           fetch_k: Optional[int] = None) -> List[List[MemoryItem]]:
+        """`vecs`: the queries' embeddings from embed_queries (skips embedding here).
+
+        `diversity` (one number or one per query, in [0, 1]; 0 = off): near-duplicate memories
+        stop crowding the hits -- the index fetches its `fetch_k` best rows per query (default
+        min(64, 4 * limit)) and picks `limit` of them by maximal marginal relevance, trading
+        (1 - diversity) * cosine-to-the-query against diversity * the largest cosine to a hit
+        already picked (SemanticIndex.search, csrc/ops/similarity_mmr.hip). Semantic mode only."""
         Q = len(queries)
         tags = list(tags) if tags is not None else [None] * Q
         minp = list(min_priority) if min_priority is not None else [0] * Q
+        div = check_diversity(diversity, Q)
+        check_fetch_k(fetch_k, max(1, min(int(limit), 64)))
+        if mode == "substring" and any(div):
+            raise ValueError("diversity re-ranking needs the semantic index: mode='substring' takes diversity=0")
         async with self._semantic_lock:
             if mode == "substring":
                 return [self._substring(q, t, p, limit) for q, t, p in zip(queries, tags, minp)]
 
             def run():
                 v = self.embedder(list(queries)) if vecs is None else vecs
+                if any(div):
+                    return self.index.search(v, limit, minp, [t or () for t in tags], diversity=div, fetch_k=fetch_k)
                 return self.index.search(v, limit, minp, [t or () for t in tags])
 
             if getattr(self.index.device, "type", "cpu") == "cuda":

@@ -38,7 +38,7 @@ import torch.distributed as dist
 
 from .embedding import HashingEmbedder
 from .enhanced_memory import MemoryItem
-from .semantic_index import SemanticIndex
+from .semantic_index import SemanticIndex, check_diversity, check_fetch_k
 
 K_MAX = 64  # candidates per shard per query (the kernel's top-k bound)
 
@@ -106,10 +106,18 @@ class NodeSemanticStore:
 
     async def search_batch(self, queries: Sequence[str], tags: Optional[Sequence[Optional[Set[str]]]] = None,
                            min_priority: Optional[Sequence[int]] = None, limit: int = 5,
-                           mode: str = "semantic", vecs=None) -> List[List[MemoryItem]]:
+                           mode: str = "semantic", vecs=None, diversity=0.0,
+                           fetch_k: Optional[int] = None) -> List[List[MemoryItem]]:
+        """`diversity` / `fetch_k` belong to the store contract (memory/store_protocol.py), but
+        node-wide MMR re-ranking is out of scope: the candidates' vectors live on other ranks'
+        shards. A non-zero diversity raises ValueError."""
         if mode != "semantic":
             raise ValueError("the node-wide store answers semantic searches only")
         Q = len(queries)
+        check_fetch_k(fetch_k, max(1, min(int(limit), K_MAX)))
+        if any(check_diversity(diversity, Q)):
+            raise ValueError("the node-wide store cannot re-rank for diversity: the candidates' vectors "
+                             "live on other ranks (use diversity=0)")
         if Q == 0:
             return []
         tags = list(tags) if tags is not None else [None] * Q
@@ -130,10 +138,13 @@ class NodeSemanticStore:
         return list(await asyncio.gather(*futs))
 
     async def semantic_search(self, query: str, tags: Optional[Set[str]] = None, min_priority: int = 0,
-                              limit: int = 5) -> List[MemoryItem]:
+                              limit: int = 5, diversity: float = 0.0,
+                              fetch_k: Optional[int] = None) -> List[MemoryItem]:
+        """A non-zero `diversity` raises ValueError (search_batch)."""
         if not query:
             raise ValueError("Query cannot be empty")
-        return (await self.search_batch([query], [tags], [min_priority], limit))[0]
+        return (await self.search_batch([query], [tags], [min_priority], limit, diversity=diversity,
+                                        fetch_k=fetch_k))[0]
 
     async def store_semantic_batch(self, texts: Sequence[str], metadatas=None, tags=None, priorities=None,
                                    ttl: Optional[float] = None, vecs=None) -> List[int]:

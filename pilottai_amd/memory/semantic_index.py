@@ -39,7 +39,9 @@ class TagRegistry:
         b = self.bits.get(tag)
         if b is None:
             if not create:
-                return -1
+                # with the registry full, a tag without a bit of its own may be one of those
+                # sharing the overflow bit (they are not listed): the host re-check decides
+                return OVERFLOW_BIT if len(self.bits) >= OVERFLOW_BIT else -1
             b = len(self.bits) if len(self.bits) < OVERFLOW_BIT else OVERFLOW_BIT
             if b < OVERFLOW_BIT:
                 self.bits[tag] = b
@@ -61,6 +63,36 @@ class TagRegistry:
 
 
 STORAGES = ("bf16", "q16")
+
+
+def check_diversity(diversity, Q: int) -> List[float]:
+    """The per-query MMR diversity values of a batch of Q queries: `diversity` is one number or
+    a sequence of Q numbers, each finite and in [0, 1] (ValueError otherwise)."""
+    import math
+    import numbers
+
+    if isinstance(diversity, (np.ndarray, torch.Tensor)):
+        diversity = diversity.tolist()  # a 0-d array is one number
+    vals = [diversity] * Q if isinstance(diversity, numbers.Real) else diversity
+    if isinstance(vals, (str, bytes)) or not isinstance(vals, (list, tuple, np.ndarray, torch.Tensor)):
+        raise ValueError(f"diversity must be a number in [0, 1] or one per query, not {diversity!r}")
+    vals = [v.item() if isinstance(v, (np.generic, torch.Tensor)) else v for v in vals]
+    if len(vals) != Q:
+        raise ValueError(f"diversity has {len(vals)} entries for {Q} queries")
+    for v in vals:
+        if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or not 0.0 <= v <= 1.0:
+            raise ValueError(f"diversity must be a finite number in [0, 1], not {v!r}")
+    return [float(v) for v in vals]
+
+
+def check_fetch_k(fetch_k, k: int) -> Optional[int]:
+    """`fetch_k` (the MMR candidate count) must lie in [k, 64]; None = the default min(64, 4 k)."""
+    if fetch_k is None:
+        return None
+    if isinstance(fetch_k, bool) or not isinstance(fetch_k, (int, np.integer)) \
+            or not k <= fetch_k <= ops.MMR_MAX_CANDIDATES:
+        raise ValueError(f"fetch_k must be an integer in [{k}, {ops.MMR_MAX_CANDIDATES}], not {fetch_k!r}")
+    return int(fetch_k)
 
 
 class SemanticIndex:
@@ -294,14 +326,34 @@ class SemanticIndex:
             exact.append(ex)
         return qmasks, exact
 
-    def search_tensors(self, q: torch.Tensor, k: int, min_priority, qmasks,
-                       now: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    def _mmr_planes(self) -> tuple:
+        """The row storage as ops.mmr_select takes it."""
+        return (self.hi, self.lo, self.rmeta) if self.storage == "q16" else (self.packed,)
+
+    def search_tensors(self, q: torch.Tensor, k: int, min_priority, qmasks, now: Optional[float] = None,
+                       diversity=0.0, fetch_k: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """The raw kernel pass: `q` [Q, dim] (any device, any float dtype), `min_priority` and
         `qmasks` lists or int tensors. Returns device tensors (scores [Q, k] fp32, rows [Q, k]
         int32, -1 past the hits), best first, on the index's stream (which the caller must
         order against: synchronize it or read the result inside `_stream_ctx`). Tag filters
-        on the shared overflow bit are NOT re-checked here (see `search`)."""
+        on the shared overflow bit are NOT re-checked here (see `search`).
+
+        `diversity` (a number or one per query, in [0, 1]): with any non-zero entry the pass
+        fetches the top `fetch_k` (default min(64, 4 k), at most 64) and `ops.mmr_select`
+        (csrc/ops/similarity_mmr.hip) picks k of them by maximal marginal relevance, under the same
+        lock and on the same stream; the rows then come in selection order, each with its cosine
+        score. A query with diversity 0 in such a batch comes out as its plain top-k. With every
+        entry 0 the pass is exactly the plain one."""
         k = max(1, min(int(k), 64))
+        div = check_diversity(diversity, int(q.shape[0]))
+        fetch_k = check_fetch_k(fetch_k, k)
+        mmr = any(div)
+        kk = (fetch_k or min(ops.MMR_MAX_CANDIDATES, 4 * k)) if mmr else k
+        s, r = self._pass(q, kk, min_priority, qmasks, now, (k, div) if mmr else None)
+        return s, r
+
+    def _pass(self, q: torch.Tensor, k: int, min_priority, qmasks, now: Optional[float], mmr=None):
+        """One scan for the top k; `mmr` = (picks, per-query diversity) re-ranks them (search_tensors)."""
         caller = torch.cuda.current_stream(self.device) if q.is_cuda and self.device.type == "cuda" else None
         with self._lock, self._stream_ctx():
             if caller is not None:  # `q` was produced on the caller's stream
@@ -322,23 +374,35 @@ class SemanticIndex:
             else:
                 s, r = ops.cosine_topk(qd, self.packed, self.count, k, self.priority, self.tagbits, self.expiry, minp,
                                        qt, t_now, workspace=self._ws)
+            if mmr is not None:
+                s, r = ops.mmr_select(r, s, self._mmr_planes(), mmr[0], *ops.mmr_weights(mmr[1]))
             if ev is not None:
                 ev[1].record()
                 self.pass_events.append(ev)
         return s, r
 
     def search(self, queries, k: int, min_priority: Sequence[int], tags: Sequence[Iterable[str]],
-               now: Optional[float] = None) -> List[List[Tuple[int, float]]]:
-        """Batched filtered top-k: returns per query [(row, score), ...] best first."""
+               now: Optional[float] = None, diversity=0.0,
+               fetch_k: Optional[int] = None) -> List[List[Tuple[int, float]]]:
+        """Batched filtered top-k: returns per query [(row, score), ...] best first.
+
+        `diversity` / `fetch_k`: maximal-marginal-relevance re-ranking of the top `fetch_k`
+        (search_tensors); the hits then come in selection order with their cosine scores. A
+        query whose tag filter uses the shared overflow bit has its candidates re-checked on the
+        host first, and only the survivors are re-ranked."""
         q = queries if isinstance(queries, torch.Tensor) else torch.as_tensor(np.asarray(queries, dtype=np.float32))
         Q = q.shape[0]
+        k = max(1, min(int(k), 64))
+        div = check_diversity(diversity, Q)
+        fetch_k = check_fetch_k(fetch_k, k)
         if Q == 0:
             return []
-        k = max(1, min(int(k), 64))
         tag_sets = [frozenset(t or ()) for t in tags]
         qmasks, exact = self.query_masks(tag_sets)
         if self.count == 0:
             return [[] for _ in range(Q)]
+        if any(div):
+            return self._search_mmr(q, k, list(min_priority), tag_sets, qmasks, exact, now, div, fetch_k)
         kk = k if all(exact) else min(64, 4 * k)
         s, r = self.search_tensors(q, kk, list(min_priority), qmasks, now)
         with self._stream_ctx():
@@ -356,6 +420,32 @@ class SemanticIndex:
                     break
             out.append(res)
         return out
+
+    def _search_mmr(self, q, k, minp, tag_sets, qmasks, exact, now, div, fetch_k):
+        """`search` with a non-zero diversity somewhere in the batch."""
+        Q = q.shape[0]
+        fk = fetch_k or min(ops.MMR_MAX_CANDIDATES, 4 * k)
+        if all(exact):  # scan and re-ranking in one locked pass
+            s, r = self.search_tensors(q, k, minp, qmasks, now, diversity=div, fetch_k=fk)
+        else:
+            # overflow-bit filters: the scan's candidates are re-checked exactly on the host, the
+            # survivors compacted, and only then re-ranked
+            s, r = self.search_tensors(q, fk, minp, qmasks, now)
+            with self._stream_ctx():
+                s, r = s.cpu(), r.cpu()
+            cs = torch.full((Q, fk), float("-inf"))
+            cr = torch.full((Q, fk), -1, dtype=torch.int32)
+            for i in range(Q):
+                keep = [j for j in range(fk) if r[i, j] >= 0 and
+                        (exact[i] or tag_sets[i] <= self._row_tags(int(r[i, j])))]
+                cs[i, :len(keep)] = s[i, keep]
+                cr[i, :len(keep)] = r[i, keep]
+            with self._lock, self._stream_ctx():
+                s, r = ops.mmr_select(cr.to(self.device), cs.to(self.device), self._mmr_planes(), k,
+                                      *ops.mmr_weights(div))
+        with self._stream_ctx():
+            s, r = s.cpu().numpy(), r.cpu().numpy()
+        return [[(int(row), float(sc)) for row, sc in zip(r[i], s[i]) if row >= 0] for i in range(Q)]
 
     def _stream_ctx(self):
         """Searches run on the index's own HIP stream (non-blocking w.r.t. the engine's):
@@ -545,9 +635,17 @@ class ShardedSemanticIndex:
     def add_local(self, *a, **kw) -> List[int]:
         return [r * self.world + self.rank for r in self.local.add(*a, **kw)]
 
-    def search(self, queries, k: int, min_priority, tags, now=None) -> List[List[Tuple[int, float]]]:
+    def search(self, queries, k: int, min_priority, tags, now=None, diversity=0.0,
+               fetch_k: Optional[int] = None) -> List[List[Tuple[int, float]]]:
+        """`diversity` / `fetch_k` are accepted for SemanticIndex.search's signature, but MMR
+        re-ranking across shards is out of scope: it needs the candidates' pairwise similarities,
+        and their vectors live on other ranks. A non-zero diversity raises ValueError."""
         import torch.distributed as dist
 
+        check_fetch_k(fetch_k, max(1, min(int(k), 64)))
+        if any(check_diversity(diversity, len(queries))):
+            raise ValueError("a sharded index cannot re-rank for diversity: the candidates' vectors "
+                             "live on other ranks (use diversity=0)")
         res = self.local.search(queries, k, min_priority, tags, now)
         if self.world == 1:
             return res

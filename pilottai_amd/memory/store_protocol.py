@@ -25,15 +25,18 @@ class SemanticStore(Protocol):
 
     async def search_batch(self, queries: Sequence[str], tags: Optional[Sequence[Optional[Set[str]]]] = None,
                            min_priority: Optional[Sequence[int]] = None, limit: int = 5,
-                           mode: str = "semantic", vecs=None) -> List[list]:
-        """Top-`limit` MemoryItems per query; `vecs` skips embedding."""
+                           mode: str = "semantic", vecs=None, diversity=0.0,
+                           fetch_k: Optional[int] = None) -> List[list]:
+        """Top-`limit` MemoryItems per query; `vecs` skips embedding. `diversity` (a number or
+        one per query, in [0, 1]) asks for MMR re-ranking of the `fetch_k` best hits; a store that
+        cannot do it raises ValueError for a non-zero value."""
 
     async def store_semantic_batch(self, texts: Sequence[str], metadatas=None, tags=None, priorities=None,
                                    ttl: Optional[float] = None, vecs=None) -> List[int]:
         """Append items; returns their (global) row ids; `vecs` skips embedding."""
 
     async def semantic_search(self, query: str, tags: Optional[Set[str]] = None, min_priority: int = 0,
-                              limit: int = 5) -> list:
+                              limit: int = 5, diversity: float = 0.0, fetch_k: Optional[int] = None) -> list:
         ...
 
     async def store_semantic(self, text: str, metadata=None, tags: Optional[Set[str]] = None, priority: int = 0,

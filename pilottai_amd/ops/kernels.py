@@ -488,6 +488,56 @@ def q16_topk(queries, hi, lo, rmeta, n_valid: int, K: int, row_priority, row_tag
                         q_min_priority, q_tags, now)
 
 
+MMR_MAX_CANDIDATES = 64  # candidates per query of one mmr_select call (csrc/ops/similarity_mmr.hip)
+
+
+def mmr_weights(diversity) -> tuple:
+    """Per-query MMR weights (wr, wd) = (float32(1 - d), float32(d)), fp32 CPU tensors [Q]."""
+    d = torch.as_tensor(diversity, dtype=torch.float64).reshape(-1)
+    return (1.0 - d).float(), d.float()
+
+
+def mmr_select(rows, scores, planes, k: int, wr, wd, out=None):
+    """Diversity-aware re-ranking (maximal marginal relevance) of a scan's candidate lists:
+    `rows` [Q, m] int32 / `scores` [Q, m] fp32 as cosine_topk / q16_topk return them for K = m
+    (best first, rows -1 past the hits, m <= 64), `planes` the index's row storage -- (packed,)
+    for bf16, (hi, lo, rmeta) for q16 -- and `wr` / `wd` [Q] fp32 the per-query weights
+    (mmr_weights). Returns (scores [Q, k], rows [Q, k]): the greedy picks in selection order with
+    their cosine scores, (-inf, -1) past them (semantics: ops.reference.mmr_select). GPU: one
+    launch of csrc/ops/similarity_mmr.hip; q16 agrees with the reference bit for bit."""
+    planes = tuple(planes)
+    if len(planes) not in (1, 3):
+        raise ValueError("planes must be (packed,) or (hi, lo, rmeta)")
+    Q, m = rows.shape
+    k = int(k)
+    if not 1 <= m <= MMR_MAX_CANDIDATES or not 1 <= k <= MMR_MAX_CANDIDATES:
+        raise ValueError(f"mmr_select takes 1..{MMR_MAX_CANDIDATES} candidates and picks per query, not m={m}, k={k}")
+    if _on_gpu(planes[0]):
+        C = require_native()
+        dev = planes[0].device
+        out_s, out_r = out if out is not None else (torch.empty(Q, k, dtype=torch.float32, device=dev),
+                                                    torch.empty(Q, k, dtype=torch.int32, device=dev))
+        if Q == 0:
+            return out_s, out_r
+        args = (out_s, out_r, rows.to(dev, torch.int32).contiguous(), scores.to(dev, torch.float32).contiguous())
+        w = (torch.as_tensor(wr, dtype=torch.float32).to(dev).contiguous(),
+             torch.as_tensor(wd, dtype=torch.float32).to(dev).contiguous())
+        if len(planes) == 1:
+            C.mmr_select_bf16(*args, planes[0], *w, k)
+        else:
+            C.mmr_select_q16(*args, *planes, *w, k)
+        return out_s, out_r
+    out_s = torch.full((Q, k), float("-inf"))
+    out_r = torch.full((Q, k), -1, dtype=torch.int32)
+    wr = torch.as_tensor(wr, dtype=torch.float32).cpu()
+    wd = torch.as_tensor(wd, dtype=torch.float32).cpu()
+    for q in range(Q):
+        rq = rows[q].cpu()
+        sims = ref.q16_pairwise(*planes, rq) if len(planes) == 3 else ref.bf16_pairwise(planes[0], rq)
+        out_s[q], out_r[q] = ref.mmr_select(scores[q], rq, sims, k, float(wr[q]), float(wd[q]))
+    return out_s, out_r
+
+
 def skinny_gemm(x: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """y = x @ w.T via the weight-streaming MFMA kernel (csrc/ops/gemm_skinny.hip)."""
     y = out if out is not None else torch.empty(x.shape[0], w.shape[0], dtype=x.dtype, device=x.device)

@@ -533,6 +533,67 @@ def cosine_topk_from_scores(sc, n_valid, K, row_priority, row_tags, row_expiry, 
     return out_s, out_r
 
 
+def _tile_rows(plane, rows, groups: int):
+    """Row-major [m, D] copy of rows `rows` (>= 0) of a fragment-major plane [T, S, 64, w]
+    (lane 16 g + c of (t, s) holds row 16 t + c, dims (4 s + g) w .. + w)."""
+    T, S, _, w = plane.shape
+    rows = torch.as_tensor(rows).long().to(plane.device)
+    return plane.view(T, S, groups, 16, w)[rows // 16, :, :, rows % 16, :].reshape(len(rows), S * groups * w).cpu()
+
+
+def q16_pairwise(hi, lo, rmeta, rows):
+    """s_ij of the listed q16 rows (csrc/ops/similarity_mmr.hip): float32(float64(v_i . v_j) *
+    (float64(s_i) * float64(s_j))), v = 256 hi + lo, the dot products exact in int64. `rows` [m]
+    (entries < 0: a zero row). Returns [m, m] fp32."""
+    rows = torch.as_tensor(rows).long().cpu()
+    ok = rows >= 0
+    safe = rows.clamp(min=0)
+    v = 256 * _tile_rows(hi, safe, 4).long() + _tile_rows(lo, safe, 4).long()
+    v = v * ok[:, None].long()
+    sc = rmeta[safe.to(rmeta.device), 0].double().cpu() * ok.double()
+    return ((v @ v.T).double() * (sc[:, None] * sc[None, :])).float()
+
+
+def bf16_pairwise(packed, rows):
+    """s_ij of the listed bf16 rows: the dot products of the stored rows, in fp64 ([m, m] fp64;
+    the kernel accumulates the same products in fp32)."""
+    rows = torch.as_tensor(rows).long().cpu()
+    ok = rows >= 0
+    v = _tile_rows(packed, rows.clamp(min=0), 4).double() * ok[:, None].double()
+    return v @ v.T
+
+
+def mmr_select(scores, rows, sims, k: int, wr, wd):
+    """Greedy maximal-marginal-relevance selection for ONE query (csrc/ops/similarity_mmr.hip):
+    `scores` / `rows` [m] are the scan's top-m, best first, rows -1 past the hits; `sims` [m, m]
+    the candidates' pairwise similarities. Every step picks, among the open candidates, the
+    largest float32(float32(wr * rel_i) - float32(wd * M_i)) -- M_i the largest s_ij over the
+    picks so far, the subtrahend 0 at the first step -- ties to the smaller position. Returns
+    (scores [k] fp32, rows [k] int32): the picks in order with their cosine scores, (-inf, -1)
+    past them."""
+    rel = np.asarray(torch.as_tensor(scores).float().cpu().numpy(), dtype=np.float32)
+    rid = np.asarray(torch.as_tensor(rows).cpu().numpy(), dtype=np.int64)
+    S = np.asarray(torch.as_tensor(sims).float().cpu().numpy(), dtype=np.float32)
+    wr, wd = np.float32(wr), np.float32(wd)
+    bad = np.nonzero(rid < 0)[0]
+    n = int(bad[0]) if len(bad) else len(rid)
+    out_s = torch.full((k,), float("-inf"))
+    out_r = torch.full((k,), -1, dtype=torch.int32)
+    t = (wr * rel[:n]).astype(np.float32)
+    M = np.zeros(n, dtype=np.float32)
+    open_ = np.ones(n, dtype=bool)
+    for step in range(min(k, n)):
+        u = np.zeros(n, dtype=np.float32) if step == 0 else (wd * M).astype(np.float32)
+        v = (t - u).astype(np.float32)
+        cand = np.flatnonzero(open_)
+        best = int(cand[np.argmax(v[cand])])  # the first of equal maxima: the smaller position
+        out_s[step] = float(rel[best])
+        out_r[step] = int(rid[best])
+        open_[best] = False
+        M = S[:n, best].copy() if step == 0 else np.maximum(M, S[:n, best])
+    return out_s, out_r
+
+
 def pack_mask(allowed) -> torch.Tensor:
     """bool [V] -> int32 words, bit i of word i // 32 set iff token i is allowed."""
     a = np.asarray(allowed, dtype=bool)
