@@ -106,6 +106,14 @@ int pa_mmr_select_bf16(float* out_scores, int* out_rows, const int* rows, const 
 int pa_mmr_select_q16(float* out_scores, int* out_rows, const int* rows, const float* scores, const void* hi,
                       const void* lo, const float* rmeta, const float* wr, const float* wd, int Q, int m, int K,
                       int D, int nrows, hipStream_t st);
+int pa_gather_rows_bf16(void* recs, const int* rows, const void* packed, long long n, int D, int nrows,
+                        hipStream_t st);
+int pa_gather_rows_q16(void* recs, const int* rows, const void* hi, const void* lo, const float* rmeta, long long n,
+                       int D, int nrows, hipStream_t st);
+int pa_mmr_select_rows_bf16(float* out_scores, int* out_pos, const void* recs, const int* slot, const float* scores,
+                            const float* wr, const float* wd, int Q, int m, int K, int D, int nrecs, hipStream_t st);
+int pa_mmr_select_rows_q16(float* out_scores, int* out_pos, const void* recs, const int* slot, const float* scores,
+                           const float* wr, const float* wd, int Q, int m, int K, int D, int nrecs, hipStream_t st);
 long long pa_q16_topk_workspace_bytes(int Q, int N);
 int pa_q16_topk(float* out_scores, int* out_rows, int* unsafe, void* workspace, const void* queries_q,
                 const float* qmeta, const void* hi, const void* lo, const float* rmeta, int Q, int N, int D, int K,
@@ -1046,6 +1054,68 @@ void mmr_select_q16(at::Tensor out_scores, at::Tensor out_rows, at::Tensor rows,
            "mmr_select_q16");
 }
 
+// Exchange records of stored rows (csrc/ops/similarity_mmr_rows.hip): recs [n, rowbytes] uint8,
+// rowbytes = 2 D (bf16) or 2 D + 16 (q16). `rows` come from another rank: any value is allowed,
+// ids outside the planes give zero records.
+void gather_check(const at::Tensor& recs, const at::Tensor& rows, int64_t rowbytes) {
+  check_dtype(recs, at::kByte, "recs"); check_dtype(rows, at::kInt, "rows");
+  TORCH_CHECK(rows.dim() == 1 && rows.is_contiguous(), "rows must be a contiguous [n] int32 tensor");
+  TORCH_CHECK(recs.dim() == 2 && recs.is_contiguous() && recs.size(0) == rows.size(0) && recs.size(1) == rowbytes,
+              "recs must be a contiguous [n, ", rowbytes, "] uint8 tensor");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(recs.data_ptr()) % 16 == 0, "recs must be 16-byte aligned");
+}
+
+void gather_rows_bf16(at::Tensor recs, at::Tensor rows, at::Tensor packed) {
+  for (auto* t : {&recs, &rows, &packed}) check_gpu(*t, "gather_rows_bf16 arg");
+  check_dtype(packed, at::kBFloat16, "packed");
+  TORCH_CHECK(packed.dim() == 4 && packed.size(2) == 64 && packed.size(3) == 8 && packed.is_contiguous(),
+              "packed must be bf16 tiles [N/16, D/32, 64, 8] (memory/semantic_index.py)");
+  const int64_t D = packed.size(1) * 32;
+  gather_check(recs, rows, 2 * D);
+  TORCH_CHECK(packed.size(0) * 16 <= INT32_MAX, "index too large for int32 row ids");
+  check_rc(pa_gather_rows_bf16(recs.data_ptr(), rows.data_ptr<int>(), packed.data_ptr(), (long long)rows.size(0),
+                               (int)D, (int)(packed.size(0) * 16), cur_stream()),
+           "gather_rows_bf16");
+}
+
+void gather_rows_q16(at::Tensor recs, at::Tensor rows, at::Tensor hi, at::Tensor lo, at::Tensor rmeta) {
+  for (auto* t : {&recs, &rows, &hi, &lo, &rmeta}) check_gpu(*t, "gather_rows_q16 arg");
+  check_dtype(hi, at::kChar, "hi"); check_dtype(lo, at::kChar, "lo"); check_dtype(rmeta, at::kFloat, "rmeta");
+  TORCH_CHECK(hi.dim() == 4 && hi.size(2) == 64 && hi.size(3) == 16 && lo.sizes() == hi.sizes() &&
+                  hi.is_contiguous() && lo.is_contiguous(),
+              "hi / lo must be int8 planes [N/16, D/64, 64, 16] (memory/semantic_index.py storage='q16')");
+  TORCH_CHECK(rmeta.dim() == 2 && rmeta.size(1) == 2 && rmeta.is_contiguous(), "rmeta must be [N, 2]");
+  const int64_t D = hi.size(1) * 64;
+  gather_check(recs, rows, 2 * D + 16);
+  // a row id is followed only if both its tile and its scale exist
+  const int64_t nrows = std::min<int64_t>(hi.size(0) * 16, rmeta.size(0));
+  TORCH_CHECK(nrows <= INT32_MAX, "index too large for int32 row ids");
+  check_rc(pa_gather_rows_q16(recs.data_ptr(), rows.data_ptr<int>(), hi.data_ptr(), lo.data_ptr(),
+                              rmeta.data_ptr<float>(), (long long)rows.size(0), (int)D, (int)nrows, cur_stream()),
+           "gather_rows_q16");
+}
+
+// MMR re-ranking over exchange records: slot [Q, m] indexes recs [R, rowbytes]; out_pos are list
+// positions. q16 is told from bf16 by the caller (the record does not carry its format).
+void mmr_select_rows(at::Tensor out_scores, at::Tensor out_pos, at::Tensor recs, at::Tensor slot, at::Tensor scores,
+                     at::Tensor wr, at::Tensor wd, int64_t K, bool q16) {
+  for (auto* t : {&out_scores, &out_pos, &recs, &slot, &scores, &wr, &wd}) check_gpu(*t, "mmr_select_rows arg");
+  mmr_check_lists(out_scores, out_pos, slot, scores, wr, wd, K);
+  check_dtype(recs, at::kByte, "recs");
+  TORCH_CHECK(recs.dim() == 2 && recs.is_contiguous(), "recs must be a contiguous [R, rowbytes] uint8 tensor");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(recs.data_ptr()) % 16 == 0, "recs must be 16-byte aligned");
+  const int64_t rb = recs.size(1), D = (rb - (q16 ? 16 : 0)) / 2, slab = q16 ? 64 : 32;
+  TORCH_CHECK(D >= slab && D % slab == 0 && 2 * D + (q16 ? 16 : 0) == rb && (!q16 || D <= 1024),
+              "recs rows of ", rb, " bytes are not ", q16 ? "q16 records (2 D + 16, D a multiple of 64, <= 1024)"
+                                                          : "bf16 records (2 D, D a multiple of 32)");
+  TORCH_CHECK(recs.size(0) <= INT32_MAX, "too many records for int32 slots");
+  auto fn = q16 ? pa_mmr_select_rows_q16 : pa_mmr_select_rows_bf16;
+  check_rc(fn(out_scores.data_ptr<float>(), out_pos.data_ptr<int>(), recs.data_ptr(), slot.data_ptr<int>(),
+              scores.data_ptr<float>(), wr.data_ptr<float>(), wd.data_ptr<float>(), (int)slot.size(0),
+              (int)slot.size(1), (int)K, (int)D, (int)recs.size(0), cur_stream()),
+           "mmr_select_rows");
+}
+
 }  // namespace
 
 // One phase of the vocab-parallel top-k / top-p threshold (sampling.hip tp_topkp_kernel):
@@ -1332,6 +1402,9 @@ PYBIND11_MODULE(_C, m) {
   m.def("q16_topk", &q16_topk);
   m.def("mmr_select_bf16", &mmr_select_bf16);
   m.def("mmr_select_q16", &mmr_select_q16);
+  m.def("gather_rows_bf16", &gather_rows_bf16);
+  m.def("gather_rows_q16", &gather_rows_q16);
+  m.def("mmr_select_rows", &mmr_select_rows);
   m.def("car_alloc", &car_alloc);
   m.def("car_open", &car_open);
   m.def("car_close", [](int64_t p) { return pa_car_close((void*)(uintptr_t)p); });

@@ -27,65 +27,12 @@
 // to LDS; wave 0 then selects with one lane per candidate (M_i in a register, wave argmax by
 // max + ballot, the winner's column read from LDS). Lanes past the list and lists' -1 entries
 // never form an address from their row id: they read a listed row's fragment and zero it.
-#include <cfloat>
-
 #include "common.h"
+#include "mmr_common.h"
 #include "q16_exact.h"
 
 namespace pa {
 namespace mmr {
-
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int MAXM = 64;       // candidates per query
-constexpr int THREADS = 256;   // 4 waves
-constexpr int NG = MAXM / 16;  // candidate groups
-constexpr int SLD = MAXM + 4;  // padded LDS row (floats): the block stores spread over the banks
-
-// Length of the list whose entry `lane` is `row`: the leading entries that name a stored row.
-__device__ __forceinline__ int list_len(int row, int nrows) {
-  const unsigned long long bad = ~__ballot(row >= 0 && row < nrows);
-  return bad ? __ffsll((long long)bad) - 1 : 64;
-}
-
-// Wave 0: the greedy selection over sim[j * SLD + i] = s_ij (see the header). Lane i holds
-// candidate i of the n listed. The product and the difference must round separately: this file
-// is compiled with -ffp-contract=off (pilottai_amd/_build.py FILE_FLAGS).
-__device__ __forceinline__ void select(float* __restrict__ out_s, int* __restrict__ out_r, const float* sim,
-                                       float rel, int row, int n, int K, float wr, float wd) {
-  const int lane = threadIdx.x & 63;
-  const int picks = min(K, n);
-  bool open = lane < n;
-  const float t = wr * rel;
-  float M = 0.f;
-  for (int step = 0; step < picks; ++step) {
-    const float u = step == 0 ? 0.f : wd * M;
-    const float key = open ? t - u : -FLT_MAX;
-    const float best = wave_max(key);
-    unsigned long long hit = __ballot(open && key == best);
-    if (!hit) hit = __ballot(open);  // unreachable for finite scores
-    const int w = __ffsll((long long)hit) - 1;
-    const float ws = __shfl(rel, w, 64);
-    const int wrow = __shfl(row, w, 64);
-    if (lane == 0) {
-      out_s[step] = ws;
-      out_r[step] = wrow;
-    }
-    if (lane == w) open = false;
-    const float s = sim[w * SLD + lane];
-    M = step == 0 ? s : fmaxf(M, s);
-  }
-  for (int j = picks + lane; j < K; j += 64) {
-    out_s[j] = -INFINITY;
-    out_r[j] = -1;
-  }
-}
-
-// this wave's A fragment: group `wid` of the four gathered (wave-uniform select, no indexing)
-template <typename V>
-__device__ __forceinline__ V pick_group(const V (&f)[NG], int wid) {
-  return wid == 0 ? f[0] : (wid == 1 ? f[1] : (wid == 2 ? f[2] : f[3]));
-}
 
 template <bool Q16>
 __global__ __launch_bounds__(THREADS) void mmr_kernel(
@@ -210,10 +157,6 @@ __global__ __launch_bounds__(THREADS) void mmr_kernel(
     const float rel = lane < n ? scores[(size_t)q * m + lane] : 0.f;
     select(out_s + (size_t)q * K, out_r + (size_t)q * K, sim, rel, row, n, K, wr[q], wd[q]);
   }
-}
-
-inline bool bad_shape(int m, int K, int D, int slab) {
-  return m < 1 || m > MAXM || K < 1 || K > MAXM || D < slab || D % slab != 0;
 }
 
 }  // namespace mmr

@@ -33,10 +33,12 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # Per-file code-generation flags. gemm_mid.hip: MFMA accumulators in the VGPR form; with
 # the AGPR form hipcc shuffles them through v_accvgpr moves in the software-pipelined loop.
 # similarity_mmr.hip: the MMR value is three separately rounded fp32 operations (the reference's),
-# so the product must not be contracted into an fma with the difference.
+# so the product must not be contracted into an fma with the difference; similarity_mmr_rows.hip
+# runs the same selection (csrc/ops/mmr_common.h) over exchange records.
 FILE_FLAGS = {"gemm_mid.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
               "gemm_stream.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
-              "similarity_mmr.hip": ["-ffp-contract=off"]}
+              "similarity_mmr.hip": ["-ffp-contract=off"],
+              "similarity_mmr_rows.hip": ["-ffp-contract=off"]}
 
 
 def _torch_paths():

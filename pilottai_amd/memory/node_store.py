@@ -16,7 +16,11 @@ process per GPU that store must be node-wide, not one private copy per rank:
   query vectors (RCCL over xGMI on GPUs), scan the local shard once for every rank's queries
   (one streaming pass of the HIP cosine top-k kernel, filters in-kernel), all-gather the
   (global row, score) candidates, and merge each rank's own queries' top-k.
-  A write made on rank A in one round is visible to a search from rank B in the same round.
+  A write made on rank A in one round is visible to a search from rank B in the same round;
+* built with cross_shard_mmr=True, a query with a non-zero `diversity` is re-ranked by maximal
+  marginal relevance over its merged candidates: the round fetches their stored rows from the
+  owning shards as exchange records (two more all-to-alls, csrc/ops/similarity_mmr_rows.hip)
+  and selects where the query was asked (_mmr_round).
 
 Tags are exchanged as strings (each shard maps them to its own filter bits), expiry is
 wall-clock. With world == 1 the store degenerates to a local index (no collectives).
@@ -27,6 +31,7 @@ xGMI; on CPU the shared-memory plane too).
 from __future__ import annotations
 
 import asyncio
+import os
 import threading
 import time
 from datetime import datetime, timedelta
@@ -38,18 +43,23 @@ import torch.distributed as dist
 
 from .embedding import HashingEmbedder
 from .enhanced_memory import MemoryItem
-from .semantic_index import SemanticIndex, check_diversity, check_fetch_k
+from .semantic_index import SemanticIndex, check_diversity, check_fetch_k, merge_candidates, select_from_records
 
 K_MAX = 64  # candidates per shard per query (the kernel's top-k bound)
 
 
 class NodeSemanticStore:
     def __init__(self, index: SemanticIndex, embedder=None, group=None, cpu_group=None, max_queries: int = 64,
-                 fallback_text: Optional[Callable[[int], str]] = None, idle_s: float = 0.002):
+                 fallback_text: Optional[Callable[[int], str]] = None, idle_s: float = 0.002,
+                 cross_shard_mmr: bool = False):
         """index: this rank's shard. group: the process group of the agent-DP ranks (device
         collectives: RCCL on GPUs); cpu_group: a gloo group over the same ranks (host metadata;
-        defaults to `group` when that is gloo). max_queries: queries per rank per round."""
+        defaults to `group` when that is gloo). max_queries: queries per rank per round.
+        cross_shard_mmr: answer `diversity=` searches by fetching the candidates' rows from their
+        shards (every rank must agree: a mismatch fails the store); PILOTTAI_NODE_MMR=1 turns the
+        default on. Off, a non-zero diversity raises ValueError."""
         self.index = index
+        self.cross_shard_mmr = bool(cross_shard_mmr) or os.environ.get("PILOTTAI_NODE_MMR", "") == "1"
         self.embedder = embedder or HashingEmbedder(index.dim)
         self.group = group
         self.cpu_group = cpu_group if cpu_group is not None else group
@@ -61,15 +71,19 @@ class NodeSemanticStore:
         self.idle_s = idle_s
         self.items: Dict[int, MemoryItem] = {}  # global row -> item (replicated)
         self._lock = threading.Lock()
-        # (vector, min_priority, tags, k, future, loop or None, raw rows wanted)
-        self._queries: List[Tuple[np.ndarray, int, Set[str], int, Any, Any, bool]] = []
+        # (vector, min_priority, tags, k, future, loop or None, raw rows wanted, diversity,
+        # MMR candidate count (0: a plain query))
+        self._queries: List[Tuple[np.ndarray, int, Set[str], int, Any, Any, bool, float, int]] = []
         self._writes: List[Tuple[np.ndarray, MemoryItem, Any, Any]] = []
         self._stop = False
         self._thread: Optional[threading.Thread] = None
         self._err: Optional[BaseException] = None
         # hits / remote_hits: returned rows, and those held by another rank's shard
         self.stats = {"rounds": 0, "idle_rounds": 0, "lookups": 0, "writes": 0, "round_s": 0.0,
-                      "scan_s": 0.0, "max_queries_round": 0, "hits": 0, "remote_hits": 0}
+                      "scan_s": 0.0, "max_queries_round": 0, "hits": 0, "remote_hits": 0,
+                      # rounds with a diverse query somewhere, this rank's diverse queries, the
+                      # records it requested for them, and the time its MMR steps took
+                      "mmr_rounds": 0, "mmr_lookups": 0, "mmr_rows": 0, "mmr_s": 0.0}
         self._dev_coll = self._pick_device()
         # host payloads (counts, filters, tags, items; on CPU also vectors and candidates) go
         # through a shared-memory all-gather between the node's ranks (parallel/host_gather.py)
@@ -108,16 +122,14 @@ class NodeSemanticStore:
                            min_priority: Optional[Sequence[int]] = None, limit: int = 5,
                            mode: str = "semantic", vecs=None, diversity=0.0,
                            fetch_k: Optional[int] = None) -> List[List[MemoryItem]]:
-        """`diversity` / `fetch_k` belong to the store contract (memory/store_protocol.py), but
-        node-wide MMR re-ranking is out of scope: the candidates' vectors live on other ranks'
-        shards. A non-zero diversity raises ValueError."""
+        """`diversity` (a number or one per query) / `fetch_k`: MMR re-ranking of the `fetch_k`
+        best merged hits (memory/store_protocol.py). The candidates' vectors live on other ranks'
+        shards: a store built with cross_shard_mmr=True fetches them in the round (_mmr_round);
+        any other raises ValueError for a non-zero diversity."""
         if mode != "semantic":
             raise ValueError("the node-wide store answers semantic searches only")
         Q = len(queries)
-        check_fetch_k(fetch_k, max(1, min(int(limit), K_MAX)))
-        if any(check_diversity(diversity, Q)):
-            raise ValueError("the node-wide store cannot re-rank for diversity: the candidates' vectors "
-                             "live on other ranks (use diversity=0)")
+        _, div, fks = self._check_mmr(diversity, fetch_k, int(limit), Q)
         if Q == 0:
             return []
         tags = list(tags) if tags is not None else [None] * Q
@@ -133,14 +145,14 @@ class NodeSemanticStore:
             for i in range(Q):
                 f = loop.create_future()
                 self._queries.append((vecs[i], int(minp[i]), set(tags[i] or ()), max(1, min(int(limit), K_MAX)),
-                                      f, loop, False))
+                                      f, loop, False, div[i], fks[i]))
                 futs.append(f)
         return list(await asyncio.gather(*futs))
 
     async def semantic_search(self, query: str, tags: Optional[Set[str]] = None, min_priority: int = 0,
                               limit: int = 5, diversity: float = 0.0,
                               fetch_k: Optional[int] = None) -> List[MemoryItem]:
-        """A non-zero `diversity` raises ValueError (search_batch)."""
+        """`diversity` / `fetch_k`: see search_batch."""
         if not query:
             raise ValueError("Query cannot be empty")
         return (await self.search_batch([query], [tags], [min_priority], limit, diversity=diversity,
@@ -178,6 +190,24 @@ class NodeSemanticStore:
 
     def __len__(self) -> int:
         return len(self.items)
+
+    def _check_mmr(self, diversity, fetch_k, limit, Q: int) -> Tuple[List[int], List[float], List[int]]:
+        """Per query (k, diversity, MMR candidate count; 0 for a plain query) of a validated
+        call; `limit` and `fetch_k` are one value or (search_rows_blocking) one per query."""
+        seq = (list, tuple)
+        if not isinstance(limit, seq) and not isinstance(fetch_k, seq):
+            check_fetch_k(fetch_k, max(1, min(int(limit), K_MAX)))  # also for an empty batch
+        ks = [max(1, min(int(k), K_MAX)) for k in (limit if isinstance(limit, seq) else [limit] * Q)]
+        fks = list(fetch_k) if isinstance(fetch_k, seq) else [fetch_k] * Q
+        if len(ks) != Q or len(fks) != Q:
+            raise ValueError(f"k / fetch_k must be one value or one per query ({Q})")
+        fks = [check_fetch_k(f, k) for f, k in zip(fks, ks)]
+        div = check_diversity(diversity, Q)
+        if any(div) and not self.cross_shard_mmr:
+            raise ValueError("the node-wide store cannot re-rank for diversity: the candidates' vectors "
+                             "live on other ranks (use diversity=0, or build the store with "
+                             "cross_shard_mmr=True on every rank)")
+        return ks, div, [(f or min(K_MAX, 4 * k)) if d > 0 else 0 for f, k, d in zip(fks, ks, div)]
 
     def _check(self):
         if self._err is not None:
@@ -273,13 +303,21 @@ class NodeSemanticStore:
         tensors packed on the device, and object gathers only for what has no fixed shape:
         the written items (rounds with writes) and query tag strings (rounds with tags). The
         host payloads travel through the node's shared-memory plane (HostGather), microseconds
-        per all-gather instead of a gloo loopback-TCP round trip."""
+        per all-gather instead of a gloo loopback-TCP round trip. A round in which some rank has
+        a diverse query (header word 4) adds _mmr_round's: one 1-int host gather and two more
+        all-to-alls (row requests, exchange records); any other round issues none of them."""
         with self._lock:
             qs, self._queries = self._queries[:self.max_queries], self._queries[self.max_queries:]
             ws, self._writes = self._writes, []
         any_tags = any(q[2] for q in qs)
-        hdr = torch.tensor([len(qs), len(ws), int(bool(self._stop)), int(any_tags)], dtype=torch.int64)
+        # word 4: bit 0 the cross_shard_mmr flag (every rank must agree), bit 1 a diverse query
+        mmr_word = int(self.cross_shard_mmr) | (2 if any(q[8] for q in qs) else 0)
+        hdr = torch.tensor([len(qs), len(ws), int(bool(self._stop)), int(any_tags), mmr_word], dtype=torch.int64)
         hdr = self._gather_host(hdr)
+        if int((hdr[:, 4] & 1).min()) != int((hdr[:, 4] & 1).max()):
+            raise RuntimeError("cross_shard_mmr differs between the ranks of the node-wide store: "
+                               f"{(hdr[:, 4] & 1).tolist()} (every rank must be built with the same value)")
+        any_div = bool((hdr[:, 4] & 2).any())
         nq = hdr[:, 0].tolist()
         nw = hdr[:, 1].tolist()
         if sum(nq) == 0 and sum(nw) == 0:
@@ -315,7 +353,8 @@ class NodeSemanticStore:
         allv = self._gather_tensor(qv.to(self._dev_coll))  # [W, QM, dim]
         meta = torch.zeros(QM, 2, dtype=torch.int64)
         if qs:
-            meta[:len(qs)] = torch.from_numpy(np.array([(q[1], q[3]) for q in qs], dtype=np.int64))
+            # a diverse query scans for its MMR candidate count, a plain one for its k
+            meta[:len(qs)] = torch.from_numpy(np.array([(q[1], q[8] or q[3]) for q in qs], dtype=np.int64))
         allm = self._gather_host(meta)  # [W, QM, 2]
         kmax = int(allm[:, :, 1].max())
         alltags = self._gather_obj([sorted(q[2]) for q in qs]) if bool(hdr[:, 3].any()) else [[]] * W
@@ -362,18 +401,87 @@ class NodeSemanticStore:
         ms = top_s.cpu().numpy()
         mr = torch.gather(mr[:len(qs)], 1, order).cpu().numpy()
         nhit = (mr >= 0).sum(axis=1)
-        for i, q in enumerate(qs):
-            got = mr[i, :min(int(nhit[i]), q[3])]
-            self.stats["hits"] += len(got)
-            self.stats["remote_hits"] += int((got % W != self.rank).sum())
+        res = []
         for i, q in enumerate(qs):
             m = min(int(nhit[i]), q[3])
-            rows = list(zip(mr[i, :m].tolist(), ms[i, :m].tolist()))
-            _deliver(q[4], q[5], rows if q[6] else self._items_for(rows))
+            res.append(list(zip(mr[i, :m].tolist(), ms[i, :m].tolist())))
+        if any_div:  # every rank joins the request / record exchanges, with or without diverse queries
+            for i, rows in self._mmr_round(qs, alls, allr, QM, kmax).items():
+                res[i] = rows
+        for i, q in enumerate(qs):
+            self.stats["hits"] += len(res[i])
+            self.stats["remote_hits"] += sum(1 for g, _ in res[i] if g % W != self.rank)
+        for i, q in enumerate(qs):
+            _deliver(q[4], q[5], res[i] if q[6] else self._items_for(res[i]))
         self.stats["lookups"] += len(qs)
         self.stats["max_queries_round"] = max(self.stats["max_queries_round"], sum(nq))
         self.stats["round_s"] += time.perf_counter() - t0
         return True, False
+
+    def _mmr_round(self, qs, alls: torch.Tensor, allr: torch.Tensor, QM: int, kmax: int) -> Dict[int, list]:
+        """The MMR steps of a round in which some rank has a diverse query; every rank calls it.
+        alls / allr [W shards, QM, kmax]: the exchanged candidates of this rank's queries.
+        Returns {query position: [(global row, cosine), ...] in selection order} of this rank's
+        diverse queries.
+
+        Merge: a diverse query's list is its `fk` best by (score descending, global row ascending).
+        Request: the distinct rows of those lists go to their owners (g % W) as [W, R] local row
+        ids, R the node's largest per-owner count (one host-plane gather), -1 padding; the owner
+        answers with one index.gather_rows over the W R ids and the records travel back as
+        [W, R, rowbytes] in one exchange. Writes are applied only at the top of a round, so the
+        rows fetched are the rows scored. Select: slot[q][p] = owner R + j into the received
+        buffer, one ops.mmr_select_rows launch on the index's device."""
+        t0 = time.perf_counter()
+        W = self.world
+        idev = self.index.device
+        xdev = self._dev_coll if W > 1 else idev  # where the exchanged tensors live
+        self.stats["mmr_rounds"] += 1
+        didx = [i for i, q in enumerate(qs) if q[8]]
+        nd = len(didx)
+        cnt = np.zeros(W, dtype=np.int64)
+        nu = 0
+        if nd:
+            sel = torch.tensor(didx, device=alls.device)
+            ms, mr = merge_candidates(alls.permute(1, 0, 2).reshape(QM, W * kmax)[sel],
+                                      allr.permute(1, 0, 2).reshape(QM, W * kmax)[sel])
+            fkm = min(max(qs[i][8] for i in didx), W * kmax)
+            ms, mr = ms[:, :fkm].cpu(), mr[:, :fkm].cpu()
+            fk = torch.tensor([qs[i][8] for i in didx])
+            keep = (torch.arange(fkm)[None, :] < fk[:, None]) & (mr >= 0)  # a prefix of every list
+            ms = torch.where(keep, ms, torch.full_like(ms, float("-inf")))
+            mr = torch.where(keep, mr, torch.full_like(mr, -1))
+            uniq, inv = np.unique(mr[keep].numpy(), return_inverse=True)
+            nu = len(uniq)
+            owner = uniq % W
+            cnt = np.bincount(owner, minlength=W)
+            order = np.argsort(owner, kind="stable")
+            start = np.concatenate([[0], np.cumsum(cnt)[:-1]])
+            j = np.empty(nu, dtype=np.int64)
+            j[order] = np.arange(nu) - start[owner[order]]
+        R = int(self._gather_host(torch.tensor([int(cnt.max())], dtype=torch.int64)).max())
+        out: Dict[int, list] = {i: [] for i in didx}
+        if R:  # (no rank's diverse query has a hit: nothing to fetch, every rank skips alike)
+            req = torch.full((W, R), -1, dtype=torch.int32)
+            if nu:
+                req[torch.from_numpy(owner), torch.from_numpy(j)] = torch.from_numpy(uniq // W).int()
+            got = self._exchange(req.to(xdev))  # row o: the local rows rank o wants from this shard
+            recs = self.index.gather_rows(got.reshape(-1))
+            if recs.is_cuda:  # gathered on the index's stream: order this round's stream behind it
+                torch.cuda.current_stream(recs.device).wait_stream(self.index._stream)
+            recs = self._exchange(recs.view(W, R, -1).to(xdev))  # row o: owner o's records for this rank
+            if nd:
+                slot = torch.full(mr.shape, -1, dtype=torch.int32)
+                slot[keep] = torch.from_numpy((owner * R + j)[inv]).int()
+                kk = max(qs[i][3] for i in didx)  # the first k picks do not depend on how many follow
+                s, g = select_from_records(recs.reshape(W * R, -1), slot, ms, mr, kk, [qs[i][7] for i in didx], idev,
+                                           self.index.storage == "q16")
+                for n, i in enumerate(didx):
+                    out[i] = [(int(row), float(sc)) for row, sc in
+                              zip(g[n, :qs[i][3]].tolist(), s[n, :qs[i][3]].tolist()) if row >= 0]
+        self.stats["mmr_lookups"] += nd
+        self.stats["mmr_rows"] += nu
+        self.stats["mmr_s"] += time.perf_counter() - t0
+        return out
 
     def _items_for(self, rows: List[Tuple[int, float]]) -> List[MemoryItem]:
         """Replicated items of merged hits, best first, then ordered like EnhancedMemory
@@ -391,17 +499,21 @@ class NodeSemanticStore:
 
     # ------------------------------------------------------------------ raw candidates (tests, tools)
     def search_rows_blocking(self, vecs: np.ndarray, k: int, min_priority: Sequence[int],
-                             tags: Sequence[Sequence[str]], timeout: float = 120.0) -> List[List[Tuple[int, float]]]:
+                             tags: Sequence[Sequence[str]], timeout: float = 120.0, diversity=0.0,
+                             fetch_k: Optional[int] = None) -> List[List[Tuple[int, float]]]:
         """From any thread: enqueue raw query vectors for the next round and wait for their
-        merged [(global row, score), ...] lists (the store thread must be running)."""
+        merged [(global row, score), ...] lists (the store thread must be running). `diversity`
+        / `fetch_k` as in search_batch: a diverse query's rows come in selection order. `k` and
+        `fetch_k` may be lists with one entry per query (one call is one round's worth)."""
         import concurrent.futures as cf
 
+        ks, div, fks = self._check_mmr(diversity, fetch_k, k, len(vecs))
         futs = [cf.Future() for _ in range(len(vecs))]
         with self._lock:
             self._check()
             for i, v in enumerate(vecs):
                 self._queries.append((np.asarray(v, np.float32), int(min_priority[i]), set(tags[i] or ()),
-                                      max(1, min(int(k), K_MAX)), futs[i], None, True))
+                                      ks[i], futs[i], None, True, div[i], fks[i]))
         return [f.result(timeout) for f in futs]
 
     def store_rows_blocking(self, vecs: np.ndarray, items: Sequence[MemoryItem], timeout: float = 120.0) -> List[int]:

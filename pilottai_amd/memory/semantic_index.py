@@ -15,7 +15,9 @@ eviction (pilott/memory/enhanced_memory.py:27) without its stale-index bug
 Tags map to bits 0..62 through a registry; further distinct tags share bit 63
 and are re-checked exactly on the host for the (few) returned candidates.
 `ShardedSemanticIndex` splits rows across ranks and merges per-rank top-k with
-one all-gather (RCCL over xGMI).
+one all-gather (RCCL over xGMI). Diversity-aware (MMR) re-ranking runs behind the scan
+(csrc/ops/similarity_mmr.hip); across shards the candidates' rows travel as exchange records
+(`gather_rows`, `merge_candidates`, `select_from_records`; csrc/ops/similarity_mmr_rows.hip).
 """
 from __future__ import annotations
 
@@ -93,6 +95,35 @@ def check_fetch_k(fetch_k, k: int) -> Optional[int]:
             or not k <= fetch_k <= ops.MMR_MAX_CANDIDATES:
         raise ValueError(f"fetch_k must be an integer in [{k}, {ops.MMR_MAX_CANDIDATES}], not {fetch_k!r}")
     return int(fetch_k)
+
+
+def merge_candidates(scores: torch.Tensor, rows: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Merged candidate lists of several shards: `scores` [Q, C] fp32 / `rows` [Q, C] int64 global
+    rows (-1 with score -inf: no candidate), each list sorted by (score descending, global row
+    ascending) with the misses last. Two stable sorts, so equal scores -- exact copies of one
+    row on different shards -- come out in one order whatever the shard count (torch.topk leaves
+    their order unspecified)."""
+    key = torch.where(rows >= 0, rows, torch.full_like(rows, torch.iinfo(torch.int64).max))
+    o = torch.sort(key, dim=1, stable=True).indices
+    s1, r1 = torch.gather(scores, 1, o), torch.gather(rows, 1, o)
+    o = torch.sort(s1, dim=1, descending=True, stable=True).indices
+    return torch.gather(s1, 1, o), torch.gather(r1, 1, o)
+
+
+def select_from_records(recs: torch.Tensor, slot: torch.Tensor, scores: torch.Tensor, rows: torch.Tensor, k: int,
+                        div: Sequence[float], device, q16: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The cross-shard MMR selection both sharded stores run: `recs` [R, rowbytes] the fetched
+    exchange records, `slot` / `scores` / `rows` [Q, m] each candidate's record, cosine and global
+    row (merged order, slot -1 past a list), `div` the per-query diversity. One
+    ops.mmr_select_rows launch on `device` (a CPU index: the reference path); the picked list
+    positions are mapped to global rows. Returns host tensors (scores [Q, k], rows [Q, k] int64),
+    (-inf, -1) past the picks."""
+    dev = torch.device(device)
+    s, pos = ops.mmr_select_rows(recs.to(dev), slot.to(dev, torch.int32), scores.to(dev, torch.float32), k,
+                                 *ops.mmr_weights(list(div)), q16=q16)
+    s, pos = s.cpu(), pos.cpu().long()
+    g = torch.gather(rows.cpu().long(), 1, pos.clamp(min=0))
+    return s, torch.where(pos >= 0, g, torch.full_like(g, -1))
 
 
 class SemanticIndex:
@@ -329,6 +360,18 @@ class SemanticIndex:
     def _mmr_planes(self) -> tuple:
         """The row storage as ops.mmr_select takes it."""
         return (self.hi, self.lo, self.rmeta) if self.storage == "q16" else (self.packed,)
+
+    def gather_rows(self, rows) -> torch.Tensor:
+        """Exchange records [n, rowbytes] uint8 (ops.gather_rows) of the local rows `rows` (any
+        int values: ids that name no stored tile give the all-zero record), on the index's device,
+        under the index lock and on its stream like a search pass (the caller orders against
+        that stream as for search_tensors). What a cross-shard MMR request is answered with."""
+        rows = torch.as_tensor(rows)
+        caller = torch.cuda.current_stream(self.device) if rows.is_cuda and self.device.type == "cuda" else None
+        with self._lock, self._stream_ctx():
+            if caller is not None:  # `rows` was produced on the caller's stream
+                torch.cuda.current_stream(self.device).wait_stream(caller)
+            return ops.gather_rows(self._mmr_planes(), rows.reshape(-1).to(self.device, torch.int32))
 
     def search_tensors(self, q: torch.Tensor, k: int, min_priority, qmasks, now: Optional[float] = None,
                        diversity=0.0, fetch_k: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -608,11 +651,17 @@ class ShardedSemanticIndex:
     Inserts go to the local shard (global row = local_row * world + rank); a
     search runs the local top-k and merges all ranks' candidates with one
     all-gather. All ranks must call `search` collectively with the same queries.
+    With cross_shard_mmr=True a search with a non-zero `diversity` also all-gathers the
+    merged candidates' stored rows (exchange records) and re-ranks them on every rank.
     """
 
-    def __init__(self, local: SemanticIndex, group=None):
+    def __init__(self, local: SemanticIndex, group=None, cross_shard_mmr: bool = False):
+        """cross_shard_mmr: answer search(diversity=) by fetching the merged candidates' stored
+        rows from their shards (every rank must pass the same value); off, a non-zero diversity
+        raises ValueError."""
         import torch.distributed as dist
 
+        self.cross_shard_mmr = bool(cross_shard_mmr)
         self.local = local
         self.group = group
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
@@ -637,15 +686,19 @@ class ShardedSemanticIndex:
 
     def search(self, queries, k: int, min_priority, tags, now=None, diversity=0.0,
                fetch_k: Optional[int] = None) -> List[List[Tuple[int, float]]]:
-        """`diversity` / `fetch_k` are accepted for SemanticIndex.search's signature, but MMR
-        re-ranking across shards is out of scope: it needs the candidates' pairwise similarities,
-        and their vectors live on other ranks. A non-zero diversity raises ValueError."""
+        """`diversity` / `fetch_k`: MMR re-ranking as SemanticIndex.search does it needs the
+        candidates' pairwise similarities, and their vectors live on other ranks. Built with
+        cross_shard_mmr=True the search fetches them (_search_mmr); otherwise a non-zero
+        diversity raises ValueError."""
         import torch.distributed as dist
 
-        check_fetch_k(fetch_k, max(1, min(int(k), 64)))
-        if any(check_diversity(diversity, len(queries))):
-            raise ValueError("a sharded index cannot re-rank for diversity: the candidates' vectors "
-                             "live on other ranks (use diversity=0)")
+        div = check_diversity(diversity, len(queries))
+        fetch_k = check_fetch_k(fetch_k, max(1, min(int(k), 64)))
+        if any(div):
+            if not self.cross_shard_mmr:
+                raise ValueError("a sharded index cannot re-rank for diversity: the candidates' vectors "
+                                 "live on other ranks (use diversity=0, or build it with cross_shard_mmr=True)")
+            return self._search_mmr(queries, max(1, min(int(k), 64)), min_priority, tags, now, div, fetch_k)
         res = self.local.search(queries, k, min_priority, tags, now)
         if self.world == 1:
             return res
@@ -668,3 +721,46 @@ class ShardedSemanticIndex:
             order = torch.argsort(cand[:, 1], descending=True)[:k]
             out.append([(int(cand[j, 0]), float(cand[j, 1])) for j in order])
         return out
+
+    def _search_mmr(self, queries, k, min_priority, tags, now, div, fetch_k):
+        """Cross-shard MMR: all-gather every shard's `fk` candidates and merge them
+        (merge_candidates); every rank gathers the exchange records of the merged rows it owns
+        (SemanticIndex.gather_rows, zero records for the others'); all-gather the records and
+        take each candidate's from its owner (no summing: -0 + 0 would flip a sign bit); then
+        one ops.mmr_select_rows launch locally. A query with diversity 0 comes out as its plain
+        merged top-k (weights (1, 0))."""
+        import torch.distributed as dist
+
+        W = self.world
+        fk = fetch_k or min(ops.MMR_MAX_CANDIDATES, 4 * k)
+        res = self.local.search(queries, fk, min_priority, tags, now)
+        Q = len(res)
+        if Q == 0:
+            return []
+        t = torch.full((Q, fk, 2), -1.0, dtype=torch.float64)  # fp32 scores are exact in fp64
+        t[:, :, 1] = float("-inf")
+        for i, lst in enumerate(res):
+            for j, (row, sc) in enumerate(lst[:fk]):
+                t[i, j, 0] = row * W + self.rank
+                t[i, j, 1] = sc
+        dev = self.local.device if W > 1 and dist.get_backend(self.group) == "nccl" else torch.device("cpu")
+        if W > 1:
+            flat = torch.empty((W * Q, fk, 2), dtype=t.dtype, device=dev)
+            dist.all_gather_into_tensor(flat, t.to(dev), group=self.group)
+            t = flat.view(W, Q, fk, 2).permute(1, 0, 2, 3).reshape(Q, W * fk, 2).cpu()
+        ms, mr = merge_candidates(t[:, :, 1].float(), t[:, :, 0].long())
+        ms, mr = ms[:, :fk].contiguous(), mr[:, :fk].contiguous()
+        mine = (mr >= 0) & (mr % W == self.rank)
+        recs = self.local.gather_rows(torch.where(mine, mr // W, torch.full_like(mr, -1)).reshape(-1))
+        if recs.is_cuda:
+            self.local._stream.synchronize()
+        if W > 1:
+            recs = recs.to(dev)
+            allr = torch.empty((W * Q * fk, recs.shape[1]), dtype=recs.dtype, device=dev)
+            dist.all_gather_into_tensor(allr, recs, group=self.group)
+            owner = (mr % W).clamp(min=0).reshape(-1).to(dev)
+            recs = allr.view(W, Q * fk, -1)[owner, torch.arange(Q * fk, device=dev)]
+        slot = torch.where(mr >= 0, torch.arange(Q * fk).view(Q, fk), torch.full_like(mr, -1))
+        s, g = select_from_records(recs, slot, ms, mr, k, div, self.local.device, self.local.storage == "q16")
+        return [[(int(row), float(sc)) for row, sc in zip(g[i].tolist(), s[i].tolist()) if row >= 0]
+                for i in range(Q)]

@@ -29,7 +29,9 @@ class SemanticStore(Protocol):
                            fetch_k: Optional[int] = None) -> List[list]:
         """Top-`limit` MemoryItems per query; `vecs` skips embedding. `diversity` (a number or
         one per query, in [0, 1]) asks for MMR re-ranking of the `fetch_k` best hits; a store that
-        cannot do it raises ValueError for a non-zero value."""
+        cannot do it raises ValueError for a non-zero value. EnhancedMemory always can; the
+        node-wide store can when built with cross_shard_mmr=True on every rank (it then fetches
+        the candidates' rows from their shards within the round), and refuses otherwise."""
 
     async def store_semantic_batch(self, texts: Sequence[str], metadatas=None, tags=None, priorities=None,
                                    ttl: Optional[float] = None, vecs=None) -> List[int]:

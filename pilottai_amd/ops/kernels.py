@@ -538,6 +538,87 @@ def mmr_select(rows, scores, planes, k: int, wr, wd, out=None):
     return out_s, out_r
 
 
+def record_bytes(dim: int, q16: bool) -> int:
+    """Bytes of one exchange record of a stored row (csrc/ops/similarity_mmr_rows.hip)."""
+    return 2 * int(dim) + (16 if q16 else 0)
+
+
+def gather_rows(planes, rows, out=None):
+    """Exchange records of stored rows, for MMR re-ranking where the rows' shard is not:
+    `planes` the index's row storage -- (packed,) for bf16, (hi, lo, rmeta) for q16 -- and `rows`
+    [n] int32 row ids, ANY values (they come from another rank). Returns recs [n, rowbytes]
+    uint8: per row its D bf16 values row-major (2 D bytes), or D int8 hi, D int8 lo, the fp32
+    scale and 12 zero bytes (2 D + 16); an id that names no row of the planes gives the all-zero
+    record. GPU: one launch of csrc/ops/similarity_mmr_rows.hip (gather_rows_kernel)."""
+    planes = tuple(planes)
+    if len(planes) not in (1, 3):
+        raise ValueError("planes must be (packed,) or (hi, lo, rmeta)")
+    if not _on_gpu(planes[0]):
+        rec = ref.gather_rows(planes, rows)
+        if out is not None:
+            out.copy_(rec)
+            return out
+        return rec
+    C = require_native()
+    dev = planes[0].device
+    q16 = len(planes) == 3
+    rows = torch.as_tensor(rows).to(dev, torch.int32).reshape(-1).contiguous()
+    rb = record_bytes(planes[0].shape[1] * (64 if q16 else 32), q16)
+    recs = out if out is not None else torch.empty(rows.shape[0], rb, dtype=torch.uint8, device=dev)
+    if rows.shape[0] == 0:
+        return recs
+    if q16:
+        C.gather_rows_q16(recs, rows, *planes)
+    else:
+        C.gather_rows_bf16(recs, rows, planes[0])
+    return recs
+
+
+def mmr_select_rows(recs, slot, scores, k: int, wr, wd, out=None, q16: Optional[bool] = None):
+    """mmr_select over exchange records instead of the index tiles: `recs` [R, rowbytes] uint8
+    (gather_rows), `slot` [Q, m] int32 the record of every candidate, best first -- the first entry
+    that is negative or >= R ends a list -- `scores` [Q, m] fp32 their cosines, `wr` / `wd` [Q]
+    (mmr_weights). Returns (scores [Q, k], pos [Q, k] int32): the greedy picks in selection order
+    with their cosine scores and LIST POSITIONS, (-inf, -1) past them. `q16`: the records'
+    format; None tells it from rowbytes (2 D + 16 with D a multiple of 64 is q16, 2 D with D a
+    multiple of 32 is bf16, and no length is both). GPU: one launch of
+    csrc/ops/similarity_mmr_rows.hip (mmr_rows_kernel), the tile kernel's arithmetic."""
+    R, rb = recs.shape
+    if q16 is None:
+        q16 = rb % 64 == 16
+    Q, m = slot.shape
+    k = int(k)
+    if not 1 <= m <= MMR_MAX_CANDIDATES or not 1 <= k <= MMR_MAX_CANDIDATES:
+        raise ValueError(f"mmr_select_rows takes 1..{MMR_MAX_CANDIDATES} candidates and picks per query, "
+                         f"not m={m}, k={k}")
+    if _on_gpu(recs):
+        C = require_native()
+        dev = recs.device
+        out_s, out_p = out if out is not None else (torch.empty(Q, k, dtype=torch.float32, device=dev),
+                                                    torch.empty(Q, k, dtype=torch.int32, device=dev))
+        if Q == 0:
+            return out_s, out_p
+        C.mmr_select_rows(out_s, out_p, recs, slot.to(dev, torch.int32).contiguous(),
+                          scores.to(dev, torch.float32).contiguous(),
+                          torch.as_tensor(wr, dtype=torch.float32).to(dev).contiguous(),
+                          torch.as_tensor(wd, dtype=torch.float32).to(dev).contiguous(), k, bool(q16))
+        return out_s, out_p
+    out_s = torch.full((Q, k), float("-inf"))
+    out_p = torch.full((Q, k), -1, dtype=torch.int32)
+    wr = torch.as_tensor(wr, dtype=torch.float32).cpu()
+    wd = torch.as_tensor(wd, dtype=torch.float32).cpu()
+    pair = ref.q16_record_pairwise if q16 else ref.bf16_record_pairwise
+    for q in range(Q):
+        sq = slot[q].long().cpu()
+        bad = ((sq < 0) | (sq >= R)).nonzero().flatten()
+        n = int(bad[0]) if len(bad) else m
+        pos = torch.full((m,), -1, dtype=torch.int64)
+        pos[:n] = torch.arange(n)
+        sims = pair(recs, torch.where(pos >= 0, sq, pos))
+        out_s[q], out_p[q] = ref.mmr_select(scores[q], pos, sims, k, float(wr[q]), float(wd[q]))
+    return out_s, out_p
+
+
 def skinny_gemm(x: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """y = x @ w.T via the weight-streaming MFMA kernel (csrc/ops/gemm_skinny.hip)."""
     y = out if out is not None else torch.empty(x.shape[0], w.shape[0], dtype=x.dtype, device=x.device)

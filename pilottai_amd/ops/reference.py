@@ -563,6 +563,51 @@ def bf16_pairwise(packed, rows):
     return v @ v.T
 
 
+def gather_rows(planes, rows):
+    """Exchange records of stored rows (csrc/ops/similarity_mmr_rows.hip): [n, rowbytes] uint8,
+    one row each -- bf16 `planes` = (packed,): the D bf16 values row-major (2 D bytes); q16
+    `planes` = (hi, lo, rmeta): D int8 hi, D int8 lo, the fp32 scale and 12 zero bytes. An id
+    outside [0, rows held by the planes) gives the all-zero record ("no row")."""
+    planes = tuple(planes)
+    rows = torch.as_tensor(rows).long().cpu()
+    nrows = planes[0].shape[0] * 16 if len(planes) == 1 else min(planes[0].shape[0] * 16, planes[2].shape[0])
+    ok = (rows >= 0) & (rows < nrows)
+    safe = torch.where(ok, rows, torch.zeros_like(rows))
+    if len(planes) == 1:
+        rec = _tile_rows(planes[0], safe, 4).contiguous().view(torch.uint8)
+    else:
+        hi, lo, rmeta = planes
+        sc = rmeta[safe.to(rmeta.device), 0].float().cpu().contiguous()
+        tail = torch.zeros(len(rows), 16, dtype=torch.uint8)
+        tail[:, :4] = sc.view(torch.uint8).view(len(rows), 4)
+        rec = torch.cat([_tile_rows(hi, safe, 4).contiguous().view(torch.uint8),
+                         _tile_rows(lo, safe, 4).contiguous().view(torch.uint8), tail], 1)
+    return rec * ok[:, None].to(torch.uint8)
+
+
+def q16_record_pairwise(recs, slots):
+    """q16_pairwise over exchange records: s_ij of records `slots` [m] of `recs` [R, 2 D + 16]
+    uint8 (entries < 0: a zero row). Returns [m, m] fp32."""
+    recs = recs.cpu()
+    slots = torch.as_tensor(slots).long().cpu()
+    D = (recs.shape[1] - 16) // 2
+    ok = slots >= 0
+    r = recs[slots.clamp(min=0)]
+    v = 256 * r[:, :D].contiguous().view(torch.int8).long() + r[:, D:2 * D].contiguous().view(torch.int8).long()
+    v = v * ok[:, None].long()
+    sc = r[:, 2 * D:2 * D + 4].contiguous().view(torch.float32)[:, 0].double() * ok.double()
+    return ((v @ v.T).double() * (sc[:, None] * sc[None, :])).float()
+
+
+def bf16_record_pairwise(recs, slots):
+    """bf16_pairwise over exchange records `recs` [R, 2 D] uint8: [m, m] fp64."""
+    recs = recs.cpu()
+    slots = torch.as_tensor(slots).long().cpu()
+    ok = slots >= 0
+    v = recs[slots.clamp(min=0)].contiguous().view(torch.bfloat16).double() * ok[:, None].double()
+    return v @ v.T
+
+
 def mmr_select(scores, rows, sims, k: int, wr, wd):
     """Greedy maximal-marginal-relevance selection for ONE query (csrc/ops/similarity_mmr.hip):
     `scores` / `rows` [m] are the scan's top-m, best first, rows -1 past the hits; `sims` [m, m]

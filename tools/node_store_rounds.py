@@ -5,6 +5,13 @@ R rounds; reports per-round wall time, the scan's share, and the overhead outsid
 (collectives, packing, merge), plus what an idle round costs.
 
     python tools/node_store_rounds.py --world 8 --queries 64 --rounds 20
+
+`--diversity D` (0 < D <= 1) runs the same rounds with every query diverse, on stores built with
+cross_shard_mmr=True: the round then also requests the merged candidates' rows from their shards
+and selects over the records (two more all-to-alls; mmr_ms, mmr_rows per round), so a round's
+added cost can be read next to the plain round's.
+
+    python tools/node_store_rounds.py --world 8 --queries 64 --rounds 20 --k 5 --diversity 0.5
 """
 import argparse
 import json
@@ -40,16 +47,18 @@ def _entry(rank, world, port, a, q):
     n = a.rows // world
     idx = SemanticIndex(dim=a.dim, capacity=n, device="cpu")
     idx.add(g.standard_normal((n, a.dim)).astype(np.float32), [0] * n, [()] * n, [None] * n)
-    store = NodeSemanticStore(idx, group=dist.new_group(backend="gloo"), max_queries=a.queries)
+    store = NodeSemanticStore(idx, group=dist.new_group(backend="gloo"), max_queries=a.queries,
+                              cross_shard_mmr=a.diversity > 0)
     store.start()
     qs = g.standard_normal((a.queries, a.dim)).astype(np.float32)
-    store.search_rows_blocking(qs, a.k, [0] * a.queries, [()] * a.queries)  # warm-up round
+    kw = {"diversity": a.diversity} if a.diversity > 0 else {}
+    store.search_rows_blocking(qs, a.k, [0] * a.queries, [()] * a.queries, **kw)  # warm-up round
     dist.barrier()
     s0 = dict(store.stats)
     w0 = store._host.waited_s
     t0 = time.perf_counter()
     for _ in range(a.rounds):
-        store.search_rows_blocking(qs, a.k, [0] * a.queries, [()] * a.queries)
+        store.search_rows_blocking(qs, a.k, [0] * a.queries, [()] * a.queries, **kw)
     wall = time.perf_counter() - t0
     s1 = dict(store.stats)
     waited = store._host.waited_s - w0
@@ -64,6 +73,8 @@ def _entry(rank, world, port, a, q):
                   "round_ms": 1e3 * (s1["round_s"] - s0["round_s"]) / max(1, rounds),
                   "scan_ms": 1e3 * (s1["scan_s"] - s0["scan_s"]) / max(1, rounds),
                   "peer_wait_ms": 1e3 * waited / max(1, rounds),
+                  "mmr_ms": 1e3 * (s1["mmr_s"] - s0["mmr_s"]) / max(1, rounds),
+                  "mmr_rows": (s1["mmr_rows"] - s0["mmr_rows"]) / max(1, rounds),
                   "idle_rounds_per_s": idle_n}))
     dist.destroy_process_group()
 
@@ -76,6 +87,8 @@ def main():
     ap.add_argument("--rows", type=int, default=80000)
     ap.add_argument("--dim", type=int, default=1024)
     ap.add_argument("--k", type=int, default=64)
+    ap.add_argument("--diversity", type=float, default=0.0,
+                    help="MMR diversity of every query (0: plain rounds; > 0: stores built with cross_shard_mmr)")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     ctx = mp.get_context("spawn")
@@ -98,6 +111,8 @@ def main():
     rec = {"world": a.world, "queries_per_rank": a.queries, "k": a.k, "rows": a.rows, "dim": a.dim,
            "round_ms_max": round(max(p["round_ms"] for p in per), 3),
            "scan_ms_max": round(max(p["scan_ms"] for p in per), 3),
+           "diversity": a.diversity, "mmr_ms_max": round(max(p["mmr_ms"] for p in per), 3),
+           "mmr_rows_per_round_max": round(max(p["mmr_rows"] for p in per), 1),
            "overhead_ms_max": round(max(p["round_ms"] - p["scan_ms"] for p in per), 3),
            # the round's own host work: without the scan and without waiting for slower peers
            # (on this oversubscribed 8-CPU container the peers' CPU scans skew by 10-30 ms)
