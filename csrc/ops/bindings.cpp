@@ -13,6 +13,8 @@ int pa_fused_add_rmsnorm(void* out, void* resid, const void* x, const void* w, i
 int pa_rope_cache(void* q_out, void* k_cache, void* v_cache, const void* qkv, const int* positions,
                   const int* slot_mapping, const float* cos_sin, int T, int H, int KV, int ld,
                   int block_size, int apply_rope, hipStream_t st);
+int pa_kv_copy(void* k_cache, void* v_cache, const int* n_copies, const int* copies, int max_copies,
+               int layers, int num_blocks, int KV, long layer_stride, int block_size, hipStream_t st);
 int pa_silu_mul(void* out, const void* in, int T, int F, hipStream_t st);
 int pa_paged_attention(void* out, float* part_o, float* part_ml, const void* q, const void* k_cache,
                        const void* v_cache, const int* items, const int* n_items, int max_items,
@@ -199,6 +201,31 @@ void rope_cache(at::Tensor q_out, at::Tensor k_cache, at::Tensor v_cache, at::Te
                          cos_sin.data_ptr<float>(), T, H, KV, qkv.stride(0), block,
                          apply_rope ? 1 : 0, cur_stream()),
            "rope_cache");
+}
+
+// k_cache [layers, blocks, KV, 16, 16, 8], v_cache [layers, blocks, KV, 128, 16] (one allocation each);
+// n_copies: one device word; copies: device words (donor block, new block, j) x max_copies
+void kv_copy(at::Tensor k_cache, at::Tensor v_cache, at::Tensor n_copies, at::Tensor copies) {
+  check_gpu(k_cache, "k_cache"); check_gpu(v_cache, "v_cache");
+  check_gpu(n_copies, "n_copies"); check_gpu(copies, "copies");
+  check_dtype(k_cache, at::kBFloat16, "k_cache"); check_dtype(v_cache, at::kBFloat16, "v_cache");
+  check_dtype(n_copies, at::kInt, "n_copies"); check_dtype(copies, at::kInt, "copies");
+  TORCH_CHECK(k_cache.dim() == 6 && k_cache.size(3) == 16 && k_cache.size(4) == 16 && k_cache.size(5) == 8 &&
+                  k_cache.is_contiguous(),
+              "k_cache must be a contiguous [layers, blocks, KV, 16, 16, 8]");
+  TORCH_CHECK(v_cache.dim() == 5 && v_cache.size(3) == 128 && v_cache.size(4) == 16 && v_cache.is_contiguous() &&
+                  v_cache.size(0) == k_cache.size(0) && v_cache.size(1) == k_cache.size(1) &&
+                  v_cache.size(2) == k_cache.size(2),
+              "v_cache must be a contiguous [layers, blocks, KV, 128, 16] matching k_cache");
+  TORCH_CHECK(n_copies.numel() >= 1, "n_copies: one int32 word");
+  const int64_t max_copies = copies.numel() / 3;
+  TORCH_CHECK(copies.is_contiguous() && max_copies >= 1 && max_copies <= 65535, "copies: 3 x [1, 65535] int32 words");
+  const int64_t layers = k_cache.size(0), blocks = k_cache.size(1), KV = k_cache.size(2);
+  TORCH_CHECK(layers * KV <= 65535 && blocks < (1ll << 31), "kv_copy: grid too large");
+  check_rc(pa_kv_copy(k_cache.data_ptr(), v_cache.data_ptr(), n_copies.data_ptr<int>(), copies.data_ptr<int>(),
+                      (int)max_copies, (int)layers, (int)blocks, (int)KV, (long)(blocks * KV * 2048), 16,
+                      cur_stream()),
+           "kv_copy");
 }
 
 void silu_mul(at::Tensor out, at::Tensor in) {
@@ -1372,6 +1399,7 @@ PYBIND11_MODULE(_C, m) {
         py::arg("part_size") = py::none(), py::arg("waves") = 4);
   m.def("sample_workspace_floats", &sample_workspace_floats);
   m.def("patch_pending_ids", &patch_pending_ids);
+  m.def("kv_copy", &kv_copy);
   m.def("sample", &sample, py::arg("out_tokens"), py::arg("out_keys"), py::arg("workspace"),
         py::arg("logits"), py::arg("vocab_offset"), py::arg("temperature"), py::arg("mask_class"),
         py::arg("class_masks"), py::arg("seeds"), py::arg("offsets"), py::arg("forced"),

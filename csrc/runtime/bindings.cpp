@@ -165,6 +165,44 @@ PYBIND11_MODULE(_runtime, m) {
         return out;
       });
 
+  py::class_<BlockManager>(m, "BlockManager")
+      .def(py::init<int32_t, int32_t, bool>(), py::arg("num_blocks"), py::arg("block_size") = 16,
+           py::arg("prefix_caching") = true)
+      .def("allocate", [](BlockManager& bm, int32_t n) -> py::object {
+        std::vector<int32_t> out;
+        if (!bm.allocate(n, out)) return py::none();
+        return py::cast(out);
+      })
+      .def("release", &BlockManager::release)
+      .def("add_ref", &BlockManager::add_ref)
+      .def("ref_count", [](const BlockManager& bm, int32_t b) {
+        if (b < 0 || b >= bm.num_blocks()) throw std::out_of_range("block id");
+        return bm.ref_count(b);
+      })
+      .def("lookup", [](BlockManager& bm, uint64_t hash, const std::vector<int32_t>& toks) {
+        if ((int32_t)toks.size() != bm.block_size()) throw std::invalid_argument("lookup takes one block of tokens");
+        return bm.lookup(hash, toks.data());
+      })
+      .def("register_block", [](BlockManager& bm, int32_t b, uint64_t hash, const std::vector<int32_t>& toks,
+                                uint64_t parent) {
+        if (b < 0 || b >= bm.num_blocks()) throw std::out_of_range("block id");
+        if ((int32_t)toks.size() != bm.block_size()) throw std::invalid_argument("register_block takes one block of tokens");
+        bm.register_block(b, hash, toks.data(), parent);
+      }, py::arg("block"), py::arg("hash"), py::arg("tokens"), py::arg("parent") = 0)
+      .def("register_partial", [](BlockManager& bm, int32_t b, uint64_t parent, const std::vector<int32_t>& toks) {
+        bm.register_partial(b, parent, toks.data(), (int32_t)toks.size());
+      }, py::arg("block"), py::arg("parent"), py::arg("tokens"))
+      // -> (donor block with a reference taken, common head j), or (-1, 0)
+      .def("match_head", [](BlockManager& bm, uint64_t parent, const std::vector<int32_t>& toks, int32_t max_j,
+                            int32_t min_j) {
+        int32_t j = 0;
+        const int32_t d = bm.match_head(parent, toks.data(), (int32_t)toks.size(), max_j, min_j, &j);
+        return py::make_tuple(d, j);
+      }, py::arg("parent"), py::arg("tokens"), py::arg("max_j") = 16, py::arg("min_j") = 1)
+      .def_property_readonly("num_free", &BlockManager::num_free)
+      .def_property_readonly("num_cached", &BlockManager::num_cached)
+      .def_property_readonly("num_donors", &BlockManager::num_donors);
+
   py::class_<Scheduler>(m, "Scheduler")
       .def(py::init([](const py::dict& d) {
         SchedulerConfig c;
@@ -183,6 +221,9 @@ PYBIND11_MODULE(_runtime, m) {
         if (d.contains("prefix_caching")) c.prefix_caching = d["prefix_caching"].cast<bool>();
         if (d.contains("dedup_inflight_prefix")) c.dedup_inflight_prefix = d["dedup_inflight_prefix"].cast<bool>();
         if (d.contains("max_prefix_defer")) c.max_prefix_defer = d["max_prefix_defer"].cast<int32_t>();
+        if (d.contains("same_step_prefix")) c.same_step_prefix = d["same_step_prefix"].cast<bool>();
+        if (d.contains("partial_block_reuse")) c.partial_block_reuse = d["partial_block_reuse"].cast<bool>();
+        if (d.contains("partial_block_min")) c.partial_block_min = d["partial_block_min"].cast<int32_t>();
         if (d.contains("embed_first")) c.embed_first = d["embed_first"].cast<bool>();
         if (d.contains("embed_first_max_wait")) c.embed_first_max_wait = d["embed_first_max_wait"].cast<int32_t>();
         if (d.contains("split_decode")) c.split_decode = d["split_decode"].cast<bool>();
@@ -219,6 +260,7 @@ PYBIND11_MODULE(_runtime, m) {
         d["rep_inv_r"] = L.rep_inv_r; d["rep_start"] = L.rep_start; d["rep_n"] = L.rep_n;
         d["rep_tok"] = L.rep_tok; d["rep_cap"] = L.rep_cap; d["rep_total"] = L.rep_total;
         d["score_target"] = L.score_target; d["score_total"] = L.score_total;
+        d["n_copies"] = L.n_copies; d["copy_list"] = L.copy_list; d["copy_total"] = L.copy_total;
         d["total"] = L.total;
         return d;
       })
@@ -274,6 +316,10 @@ PYBIND11_MODULE(_runtime, m) {
       .def("num_free_embed_rows", &Scheduler::num_free_embed_rows)
       .def_property_readonly("num_free_penalty_slots", &Scheduler::num_free_penalty_slots)
       .def_property_readonly("prefix_defers", &Scheduler::prefix_defers)
+      .def_property_readonly("partial_hit_tokens", &Scheduler::partial_hit_tokens)
+      .def_property_readonly("same_step_shares", &Scheduler::same_step_shares)
+      .def_property_readonly("num_donor_blocks", &Scheduler::num_donor_blocks)
+      .def("block_ref", &Scheduler::block_ref)
       .def_property_readonly("inflight_steps", &Scheduler::inflight_steps)
       .def_property_readonly("spec_rows", &Scheduler::spec_rows)
       .def_property_readonly("spec_voided", &Scheduler::spec_voided)

@@ -1,5 +1,6 @@
 #include "block_manager.h"
 
+#include <algorithm>
 #include <cstring>
 
 namespace rt {
@@ -34,6 +35,10 @@ void BlockManager::reset() {
   lru_pos_.assign(num_blocks_, lru_[0].end());
   in_lru_.assign(num_blocks_, 0);
   reused_.assign(num_blocks_, 0);
+  donors_.clear();
+  dparent_.assign(num_blocks_, 0);
+  fill_.assign(num_blocks_, 0);
+  num_donors_ = 0;
   cache_.clear();
   free_list_.clear();
   free_list_.reserve(num_blocks_);
@@ -52,15 +57,49 @@ void BlockManager::lru_push(int32_t b, int list) {
   in_lru_[b] = (char)(list + 1);
 }
 
+void BlockManager::donor_add(int32_t b, uint64_t parent, int32_t fill) {
+  if (fill_[b] > 0) {  // already listed (a partial tail that filled up): same parent, more slots
+    fill_[b] = fill;
+    return;
+  }
+  donors_[parent].push_back(b);
+  dparent_[b] = parent;
+  fill_[b] = fill;
+  ++num_donors_;
+}
+
+void BlockManager::donor_drop(int32_t b) {
+  if (fill_[b] <= 0) return;
+  auto it = donors_.find(dparent_[b]);
+  if (it != donors_.end()) {
+    std::vector<int32_t>& v = it->second;
+    auto p = std::find(v.begin(), v.end(), b);
+    if (p != v.end()) {
+      *p = v.back();
+      v.pop_back();
+    }
+    if (v.empty()) donors_.erase(it);
+  }
+  fill_[b] = 0;
+  --num_donors_;
+}
+
+void BlockManager::forget(int32_t b) {
+  if (hashed_[b]) {
+    auto it = cache_.find(hash_[b]);
+    if (it != cache_.end() && it->second == b) cache_.erase(it);
+  }
+  donor_drop(b);
+  hashed_[b] = 0;
+  reused_[b] = 0;
+  tokens_[b].clear();
+}
+
 void BlockManager::evict_one() {
   const int list = lru_[0].empty() ? 1 : 0;  // never-reused blocks first
   const int32_t b = lru_[list].front();
   lru_remove(b);
-  auto it = cache_.find(hash_[b]);
-  if (it != cache_.end() && it->second == b) cache_.erase(it);
-  hashed_[b] = 0;
-  reused_[b] = 0;
-  tokens_[b].clear();
+  forget(b);
   free_list_.push_back(b);
 }
 
@@ -80,7 +119,7 @@ bool BlockManager::allocate(int32_t n, std::vector<int32_t>& out) {
 void BlockManager::release(int32_t b) {
   if (b < 0 || b >= num_blocks_ || ref_[b] <= 0) return;
   if (--ref_[b] > 0) return;
-  if (hashed_[b] && prefix_caching_) {
+  if ((hashed_[b] || fill_[b] > 0) && prefix_caching_) {
     if (reused_[b]) {
       lru_push(b, 1);
       if ((int32_t)lru_[1].size() > num_blocks_ / 2) {  // protected segment full: demote its oldest
@@ -92,11 +131,14 @@ void BlockManager::release(int32_t b) {
       lru_push(b, 0);
     }
   } else {
-    hashed_[b] = 0;
-    reused_[b] = 0;
-    tokens_[b].clear();
+    forget(b);
     free_list_.push_back(b);
   }
+}
+
+void BlockManager::add_ref(int32_t b) {
+  if (b < 0 || b >= num_blocks_ || ref_[b] <= 0) return;
+  ++ref_[b];
 }
 
 int32_t BlockManager::lookup(uint64_t hash, const int32_t* tokens) {
@@ -113,7 +155,7 @@ int32_t BlockManager::lookup(uint64_t hash, const int32_t* tokens) {
   return b;
 }
 
-void BlockManager::register_block(int32_t b, uint64_t hash, const int32_t* tokens) {
+void BlockManager::register_block(int32_t b, uint64_t hash, const int32_t* tokens, uint64_t parent) {
   if (!prefix_caching_ || hashed_[b]) return;
   auto it = cache_.find(hash);
   if (it != cache_.end()) return;  // an identical page is already cached; keep this one private
@@ -121,6 +163,40 @@ void BlockManager::register_block(int32_t b, uint64_t hash, const int32_t* token
   hash_[b] = hash;
   hashed_[b] = 1;
   tokens_[b].assign(tokens, tokens + block_size_);
+  donor_add(b, parent, block_size_);
+}
+
+void BlockManager::register_partial(int32_t b, uint64_t parent, const int32_t* tokens, int32_t fill) {
+  if (!prefix_caching_ || b < 0 || b >= num_blocks_ || ref_[b] <= 0) return;
+  if (fill <= 0 || fill >= block_size_ || hashed_[b] || fill_[b] > 0) return;
+  tokens_[b].assign(tokens, tokens + fill);
+  donor_add(b, parent, fill);
+}
+
+int32_t BlockManager::match_head(uint64_t parent, const int32_t* tokens, int32_t n, int32_t max_j,
+                                 int32_t min_j, int32_t* j) {
+  *j = 0;
+  if (!prefix_caching_) return -1;
+  auto it = donors_.find(parent);
+  if (it == donors_.end()) return -1;
+  const int32_t cap = std::min(std::min(n, max_j), block_size_);
+  int32_t best = -1, best_j = 0;
+  for (const int32_t d : it->second) {
+    const int32_t m = std::min<int32_t>(cap, std::min<int32_t>(fill_[d], (int32_t)tokens_[d].size()));
+    int32_t c = 0;
+    while (c < m && tokens_[d][c] == tokens[c]) ++c;
+    if (c > best_j) {
+      best_j = c;
+      best = d;
+      if (c == cap) break;
+    }
+  }
+  if (best < 0 || best_j < std::max(1, min_j)) return -1;
+  lru_remove(best);
+  reused_[best] = 1;
+  ++ref_[best];
+  *j = best_j;
+  return best;
 }
 
 }  // namespace rt

@@ -11,6 +11,13 @@
 // were reused at least once (a task's shared prefix) are protected (up to half the
 // pool; the oldest protected block is demoted when it overflows). With plain LRU the
 // 64-worker bench lost 6 points of prefix-cache hits once eviction started.
+//
+// Donor index (partial-block reuse): every registered block is also listed under its PARENT's
+// hash, with the number of leading slots whose KV is valid (16 for a full block, the prompt's
+// tail length for the last, partly filled block of a finished prefill). A prompt that leaves
+// the hash chain inside a block asks match_head() for the listed block sharing the longest
+// head with it and copies those slots (csrc/ops/kv_copy.hip) instead of computing them. A
+// partial tail block is evictable like a hashed block once its last user releases it.
 #pragma once
 #include <cstdint>
 #include <list>
@@ -33,11 +40,29 @@ class BlockManager {
   // Prefix lookup: returns the block holding exactly `tokens` under `hash`, with
   // its reference taken, or -1.
   int32_t lookup(uint64_t hash, const int32_t* tokens);
-  void register_block(int32_t block, uint64_t hash, const int32_t* tokens);
+  // `parent`: the hash of the block before it (0 for a sequence's first block); the block is
+  // listed under it as a donor of all block_size slots
+  void register_block(int32_t block, uint64_t hash, const int32_t* tokens, uint64_t parent = 0);
+  // List `block`, whose first `fill` slots (0 < fill < block_size) hold the KV of `tokens`
+  // under the chain `parent`, as a donor of those slots. The caller goes on writing the slots
+  // behind them; a later register_block() of the filled block raises the entry to a full one.
+  void register_partial(int32_t block, uint64_t parent, const int32_t* tokens, int32_t fill);
+  // The donor under `parent` with the longest common head with tokens[0:n), capped at max_j
+  // and at the donor's valid slots: returns the block with a reference taken (the caller
+  // releases it once the copy is planned) and the head's length in *j, or -1 when no donor
+  // shares at least min_j tokens.
+  int32_t match_head(uint64_t parent, const int32_t* tokens, int32_t n, int32_t max_j, int32_t min_j,
+                     int32_t* j);
+  void add_ref(int32_t block);  // one more user of a block that is in use (ref > 0)
+  int32_t ref_count(int32_t block) const { return ref_[block]; }
+  int32_t num_donors() const { return num_donors_; }
   void reset();
 
  private:
   void evict_one();
+  void donor_add(int32_t b, uint64_t parent, int32_t fill);
+  void donor_drop(int32_t b);
+  void forget(int32_t b);  // the block leaves the cache: hash entry, donor entry, tokens
   int32_t num_blocks_, block_size_;
   bool prefix_caching_;
   std::vector<int32_t> ref_;
@@ -52,6 +77,12 @@ class BlockManager {
   std::vector<std::list<int32_t>::iterator> lru_pos_;
   std::vector<char> in_lru_;   // 0 = not evictable, 1 = probation, 2 = protected
   std::vector<char> reused_;   // looked up at least once since it was computed
+  // donor index: parent hash -> blocks listed under it; fill_[b] > 0 = b is listed (under
+  // dparent_[b]) and tokens_[b][0:fill_[b]) are the tokens of its valid slots
+  std::unordered_map<uint64_t, std::vector<int32_t>> donors_;
+  std::vector<uint64_t> dparent_;
+  std::vector<int32_t> fill_;
+  int32_t num_donors_ = 0;
 };
 
 }  // namespace rt

@@ -94,6 +94,9 @@ Scheduler::Scheduler(const SchedulerConfig& cfg)
   L.rep_total = o;
   L.score_target = take(L.max_seqs);
   L.score_total = o;
+  L.n_copies = L.n_items + 1;  // a word of the header's padding: every step copies it
+  L.copy_list = take(3 * L.max_seqs);
+  L.copy_total = o;
   for (int32_t r = L.max_seqs; r-- > 0;) embed_free_.push_back(r);
   for (int32_t r = std::max(0, std::min(cfg.max_num_seqs, cfg.penalty_slots)); r-- > 0;) pen_free_.push_back(r);
 }
@@ -204,9 +207,16 @@ void Scheduler::free_seq(Sequence* s, bool keep_embed_slot) {
     embed_free_.push_back(s->embed_slot);
     s->embed_slot = -1;
   }
+  drop_copy(s);
   for (int32_t b : s->blocks) bm_.release(b);
   s->blocks.clear();
   s->block_hashes.clear();
+}
+
+void Scheduler::drop_copy(Sequence* s) {
+  if (s->copy_j > 0) bm_.release(s->copy_src);
+  s->copy_src = s->copy_dst = -1;
+  s->copy_j = 0;
 }
 
 void Scheduler::preempt(Sequence* s) {
@@ -216,6 +226,7 @@ void Scheduler::preempt(Sequence* s) {
   free_seq(s, true);
   s->score_records.clear();  // a scoring request starts over: its final output is that of one run
   s->num_computed = 0;
+  s->tail_listed = false;
   s->running = false;
   s->preempted = true;
   waiting_.push_front(s);
@@ -247,11 +258,64 @@ void Scheduler::match_prefix(Sequence* s) {
     }
   }
   s->num_computed = (int32_t)s->blocks.size() * B;
-  if (s->cached_prompt_tokens < 0) {
-    s->cached_prompt_tokens = std::min(s->num_computed, s->prompt_len);
-    stat_cached_tokens_ += s->cached_prompt_tokens;
-    stat_prompt_tokens_ += s->prompt_len;
+}
+
+// Full blocks of the prompt of `s` that `r` -- planned in the step being built, r_end tokens
+// computed at its end -- holds: the common prefix in whole blocks, never the last token of `s`.
+static int32_t shareable_blocks(const Sequence* s, const Sequence* r, int32_t r_end, int32_t B) {
+  const int32_t limit = s->scoring() ? s->score_from - 1 : (int32_t)s->tokens.size() - 1;
+  const int32_t cap = std::min(std::min(limit, r_end), (int32_t)r->tokens.size());
+  int32_t c = 0;
+  while (c < cap && s->tokens[c] == r->tokens[c]) ++c;
+  return std::min<int32_t>(c / B, (int32_t)r->blocks.size());
+}
+
+int32_t Scheduler::share_same_step(Sequence* s, const Sequence* r, int32_t r_end) {
+  const int32_t B = cfg_.block_size;
+  const int32_t m = shareable_blocks(s, r, r_end, B);
+  int32_t added = 0;
+  // behind what the hash cache gave: these blocks are registered only when the step commits
+  for (int32_t b = (int32_t)s->blocks.size(); b < m; ++b) {
+    bm_.add_ref(r->blocks[b]);
+    s->blocks.push_back(r->blocks[b]);
+    ++added;
   }
+  s->num_computed = (int32_t)s->blocks.size() * B;
+  return added;
+}
+
+void Scheduler::match_partial(Sequence* s) {
+  const int32_t B = cfg_.block_size;
+  if (!cfg_.prefix_caching || !cfg_.partial_block_reuse || !copies_ok_ || s->copy_j > 0) return;
+  if (s->embed && !s->embed_last) return;
+  if (s->block_hashes.size() != s->blocks.size()) return;  // the chain's end is not a cached block
+  const int32_t base = (int32_t)s->blocks.size() * B;
+  // at least one token is computed (a scoring request: position score_from - 1)
+  const int32_t limit = s->scoring() ? s->score_from - 1 : (int32_t)s->tokens.size() - 1;
+  const int32_t max_j = std::min(B, limit - base);
+  if (max_j < std::max(1, cfg_.partial_block_min)) return;
+  if (bm_.num_free() <= std::max(1, cfg_.num_blocks / 100)) return;  // the admission watermark
+  const uint64_t parent = s->block_hashes.empty() ? 0 : s->block_hashes.back();
+  int32_t j = 0;
+  const int32_t donor = bm_.match_head(parent, s->tokens.data() + base, (int32_t)s->tokens.size() - base,
+                                       max_j, cfg_.partial_block_min, &j);
+  if (donor < 0) return;
+  if (!bm_.allocate(1, s->blocks)) {
+    bm_.release(donor);
+    return;
+  }
+  s->copy_src = donor;
+  s->copy_dst = s->blocks.back();
+  s->copy_j = j;
+  s->num_computed = base + j;
+}
+
+void Scheduler::count_cached(Sequence* s) {
+  if (s->cached_prompt_tokens >= 0) return;
+  s->cached_prompt_tokens = std::min(s->num_computed, s->prompt_len);
+  stat_cached_tokens_ += s->cached_prompt_tokens;
+  stat_prompt_tokens_ += s->prompt_len;
+  stat_partial_tokens_ += s->copy_j;
 }
 
 void Scheduler::register_full_blocks(Sequence* s) {
@@ -262,8 +326,17 @@ void Scheduler::register_full_blocks(Sequence* s) {
     const uint64_t parent = b ? s->block_hashes[b - 1] : 0;
     const int32_t* t = s->tokens.data() + (size_t)b * B;
     const uint64_t h = hash_block(parent, t, B);
-    bm_.register_block(s->blocks[b], h, t);
+    bm_.register_block(s->blocks[b], h, t, parent);
     s->block_hashes.push_back(h);
+  }
+  // the prompt's partly filled last block, once the prompt is computed: a donor of its head
+  if (cfg_.partial_block_reuse && !s->tail_listed && !s->embed && !s->scoring() &&
+      s->num_computed >= s->prompt_len) {
+    const int32_t idx = s->prompt_len / B, fill = s->prompt_len % B;
+    if (fill > 0 && idx < (int32_t)s->blocks.size() && (int32_t)s->block_hashes.size() == idx)
+      bm_.register_partial(s->blocks[idx], idx ? s->block_hashes[idx - 1] : 0,
+                           s->tokens.data() + (size_t)idx * B, fill);
+    s->tail_listed = true;
   }
 }
 
@@ -276,6 +349,7 @@ int32_t Scheduler::schedule(int32_t* buf, int32_t buf_words) {
   if (score_requested_ && buf_words < L.score_total)
     throw std::invalid_argument("scheduler: a scoring request needs a step buffer of "
                                 "layout().score_total words, stated as schedule()'s second argument");
+  copies_ok_ = buf_words >= L.copy_total;
   last_plan_.clear();
   // rows of the step (sampling rows + scoring rows) never exceed max_num_seqs. A scoring request
   // can own many: every running sequence that may sample keeps one in reserve, so decode rows are
@@ -407,17 +481,35 @@ int32_t Scheduler::schedule(int32_t* buf, int32_t buf_words) {
     if (it != emb_end)  // embeds went ahead of these prompts this step
       for (auto p = emb_end; p != waiting_.end(); ++p) ++(*p)->embed_passed;
   }
+  // same-step sharing: prefix key -> the entry of this step that computes those blocks
+  std::unordered_map<uint64_t, size_t> key_entry;
+  if (dedup && cfg_.same_step_prefix)
+    for (size_t i = 0; i < last_plan_.size(); ++i) {
+      const Planned& p = last_plan_[i];
+      if (p.spec || p.s->embed || p.s->num_computed >= 2 * B) continue;
+      const uint64_t k = prefix_key(p.s);
+      if (k) key_entry.emplace(k, i);
+    }
   std::vector<Sequence*> deferred;
   while (!waiting_.empty() && (int32_t)last_plan_.size() < cfg_.max_num_seqs &&
          (int32_t)running_.size() < cfg_.max_num_seqs && tok_budget > 0 && prefill_budget > 0) {
     Sequence* s = waiting_.front();
     const uint64_t key = (dedup && !s->embed && s->blocks.empty()) ? prefix_key(s) : 0;
+    size_t share_from = SIZE_MAX;
     if (key && inflight.count(key) && s->defer_count < cfg_.max_prefix_defer) {
-      waiting_.pop_front();
-      ++s->defer_count;
-      ++stat_prefix_defers_;
-      deferred.push_back(s);
-      continue;
+      // join the step when the other sequence's chunk covers a full block of the common prefix
+      const auto ke = key_entry.find(key);
+      if (ke != key_entry.end()) {
+        const Planned& e = last_plan_[ke->second];
+        if (shareable_blocks(s, e.s, e.s->num_computed + e.n, B) > 0) share_from = ke->second;
+      }
+      if (share_from == SIZE_MAX) {
+        waiting_.pop_front();
+        ++s->defer_count;
+        ++stat_prefix_defers_;
+        deferred.push_back(s);
+        continue;
+      }
     }
     if (s->embed && s->embed_slot < 0) {
       if (embed_free_.empty()) break;  // every pooling row is in use: wait
@@ -435,10 +527,27 @@ int32_t Scheduler::schedule(int32_t* buf, int32_t buf_words) {
     if (budget_rows && !s->embed && !s->scoring() &&
         rows_reserved + score_rows_used >= cfg_.max_num_seqs)
       break;
-    if (s->blocks.empty()) match_prefix(s);
+    int32_t shared = 0;
+    if (s->blocks.empty()) {
+      match_prefix(s);
+      if (share_from != SIZE_MAX) {
+        const Planned& e = last_plan_[share_from];
+        shared = share_same_step(s, e.s, e.s->num_computed + e.n);
+      }
+      if (shared == 0) match_partial(s);
+    }
+    // a request that is not admitted after all gives the shared blocks back: they hold KV only
+    // once the step it would have joined has run
+    auto unshare = [&]() {
+      if (shared > 0) {
+        free_seq(s, true);
+        s->num_computed = 0;
+      }
+    };
     const int32_t pending = s->compute_len() - s->num_computed;
     int32_t n = std::min(pending, std::min(tok_budget, prefill_budget));
     if (s->scoring() && (n = fit_score_rows(s, n)) <= 0) {  // no row left: the requests behind it may fit
+      unshare();
       waiting_.pop_front();
       deferred.push_back(s);
       continue;
@@ -447,15 +556,26 @@ int32_t Scheduler::schedule(int32_t* buf, int32_t buf_words) {
     const int32_t reps = rep_need(s, n);
     // never with an empty step: one backlog always fits either region
     if (pair_used + pairs > L.pair_cap || rep_used + reps > L.rep_cap) {
+      unshare();
       waiting_.pop_front();
       deferred.push_back(s);
       continue;
     }
     const int32_t need =
         (s->num_computed + n + B - 1) / B - (int32_t)s->blocks.size();
-    if (need > 0 && bm_.num_free() - need < (running_.empty() ? 0 : watermark)) break;
-    if (!ensure_blocks(s, s->num_computed + n)) break;
+    if ((need > 0 && bm_.num_free() - need < (running_.empty() ? 0 : watermark)) ||
+        !ensure_blocks(s, s->num_computed + n)) {
+      unshare();
+      break;
+    }
     waiting_.pop_front();
+    count_cached(s);
+    if (shared > 0) {
+      // the alignment trim (2b) must leave the tokens whose blocks this entry reads
+      Planned& e = last_plan_[share_from];
+      e.keep = std::max(e.keep, s->num_computed - e.s->num_computed);
+      ++stat_same_step_;
+    }
     if (s->needs_slot() && s->pen_slot < 0) {
       s->pen_slot = pen_free_.back();
       pen_free_.pop_back();
@@ -467,8 +587,11 @@ int32_t Scheduler::schedule(int32_t* buf, int32_t buf_words) {
     s->running = true;
     s->preempted = false;
     running_.push_back(s);
-    if (key && s->num_computed < 2 * B) inflight.insert(key);  // its leading blocks are computed now
     last_plan_.push_back({s, n, samples(s, n)});
+    if (key && s->num_computed < 2 * B) {  // its leading blocks are computed now
+      inflight.insert(key);
+      if (cfg_.same_step_prefix) key_entry.emplace(key, last_plan_.size() - 1);
+    }
     score_rows_used += score_rows_of(s, s->num_computed, n);
     if (budget_rows && samples(s, n)) ++rows_reserved;
     tok_budget -= n;
@@ -484,13 +607,13 @@ int32_t Scheduler::schedule(int32_t* buf, int32_t buf_words) {
     const int32_t r = T % cfg_.token_align;
     if (T > cfg_.token_align && r > 0 && r <= cfg_.align_slack) {
       int32_t cap = 0;
-      for (const Planned& p : last_plan_) cap += p.spec ? 0 : p.n - 1;
+      for (const Planned& p : last_plan_) cap += p.spec ? 0 : std::max(0, p.n - p.keep);
       if (cap >= r) {
         int32_t left = r;
         for (size_t i = last_plan_.size(); i-- > 0 && left > 0;) {
           Planned& p = last_plan_[i];
           if (p.spec) continue;
-          const int32_t cut = std::min(left, p.n - 1);
+          const int32_t cut = std::min(left, std::max(0, p.n - p.keep));
           p.n -= cut;
           left -= cut;
           p.sample = samples(p.s, p.n);
@@ -569,6 +692,9 @@ int32_t Scheduler::schedule(int32_t* buf, int32_t buf_words) {
   }
   int32_t* stg = buf + L.score_target;
   const int32_t tpw = 16 / std::max(1, cfg_.gqa_group);
+
+  int32_t* cpl = buf + L.copy_list;
+  int32_t ncopy = 0;
 
   int32_t T = 0, ns = 0, nsamp = 0, nit = 0, nparted = 0, pslot = 0;
   // decode partition size: with few decode rows, 256-key flash-decoding partitions
@@ -683,6 +809,18 @@ int32_t Scheduler::schedule(int32_t* buf, int32_t buf_words) {
     if (s->embed_slot >= 0) nembed += n;
     const int32_t nb = (ctx + B - 1) / B;
     std::memcpy(bt + (size_t)ns * L.max_blocks, s->blocks.data(), sizeof(int32_t) * nb);
+    if (s->copy_j > 0) {
+      // the head of its first own block comes from a cached one: the step's first kernel copies
+      // it. The reference on the donor is given back now that the copy is listed -- no block is
+      // allocated between here and the step's launch, and later steps run behind it.
+      if (!copies_ok_ || ncopy >= L.max_seqs)
+        throw std::logic_error("scheduler: a partial-block copy without room in the step buffer");
+      cpl[3 * ncopy] = s->copy_src;
+      cpl[3 * ncopy + 1] = s->copy_dst;
+      cpl[3 * ncopy + 2] = s->copy_j;
+      ++ncopy;
+      drop_copy(s);
+    }
     if (p.sample) {
       lr[nsamp] = T + n - 1;
       int32_t cls = -1, forced = -1;
@@ -930,6 +1068,7 @@ int32_t Scheduler::schedule(int32_t* buf, int32_t buf_words) {
   if (nit > L.max_items)  // by construction (psz guard above, max_items sizing) this cannot happen
     throw std::logic_error("scheduler: attention item list overflows max_items");
   buf[L.n_items] = nit;
+  buf[L.n_copies] = ncopy;
   if (T > 0) {
     ++stat_steps_;
     plans_.push_back(Plan{next_plan_id_++, std::move(last_plan_)});

@@ -49,6 +49,19 @@ struct SchedulerConfig {
   // cache instead of computing the same KV again.
   bool dedup_inflight_prefix = true;
   int32_t max_prefix_defer = 4;
+  // ... unless the other sequence's chunk in this very step covers at least one full block of
+  // the common prefix: then the request joins the step, its block table pointing at those blocks
+  // (in every layer the step's K and V are in the paged cache before that layer's attention runs,
+  // so its queries read them exactly as the other sequence's own queries do). Both prefix
+  // switches below are off unless asked for; the engine asks for both (EngineConfig).
+  bool same_step_prefix = false;
+  // partial-block reuse: a prompt that leaves the cached hash chain inside a block copies the
+  // common head (>= partial_block_min tokens) of the best cached block under the same parent
+  // into its own next block (BlockManager::match_head; the step's copy list, StepLayout::copy_list)
+  // instead of computing it. Applies only to steps whose buffer is stated to hold
+  // layout().copy_total words (schedule()'s second argument).
+  bool partial_block_reuse = false;
+  int32_t partial_block_min = 1;
   // waiting embedding requests (memory lookups / write-backs encoded by the serving model)
   // are admitted before waiting generation requests: they are short and an agent's next
   // step waits on them, while a generation prompt behind them loses a few tokens of budget
@@ -132,6 +145,14 @@ struct StepLayout {
   // unless the buffer is stated to be that long.
   int32_t score_target;  // [max_seqs]: the token each row scores (tokens[p + 1]), -1 = not a scoring row
   int32_t score_total;
+  // partial-block copies (csrc/ops/kv_copy.hip), behind score_total: n_copies is the word after
+  // n_items (inside the header every step copies; 0 in a step without copies), copy_list holds
+  // that many (donor block, new block, slots) triples and is written and copied only by steps
+  // that have some. copy_total is the whole buffer; a scheduler whose buffer is not stated to be
+  // that long plans no partial-block reuse.
+  int32_t n_copies;
+  int32_t copy_list;  // [3 * max_seqs]
+  int32_t copy_total;
 };
 
 constexpr int32_t COUNTS9_SCORE_BIT = 1 << 30;  // counts[9]: the step has scoring rows
@@ -248,6 +269,11 @@ struct Sequence {
   // final hidden state is summed into pooling row embed_slot), nothing is sampled
   bool embed = false;
   int32_t embed_slot = -1;
+  // partial-block reuse: the first copy_j slots of block copy_dst (the sequence's own) come from
+  // block copy_src, on which the sequence holds a reference until the step that first runs it
+  // has listed the copy; copy_j = 0: none pending
+  int32_t copy_src = -1, copy_dst = -1, copy_j = 0;
+  bool tail_listed = false;  // the prompt's partly filled last block is in the donor index
   int32_t defer_count = 0;  // steps deferred waiting for an in-flight identical prefix
   int32_t embed_passed = 0; // steps an embed-first admission put embeds ahead of this prompt
   bool preempted = false;   // lost its KV to a preemption and waits to resume
@@ -327,6 +353,12 @@ class Scheduler {
   int64_t steps() const { return stat_steps_; }
   int64_t aligned_steps() const { return stat_aligned_steps_; }
   int64_t prefix_defers() const { return stat_prefix_defers_; }
+  int64_t partial_hit_tokens() const { return stat_partial_tokens_; }  // counted in total_cached_tokens too
+  int64_t same_step_shares() const { return stat_same_step_; }         // requests that joined a prefix's own step
+  int32_t num_donor_blocks() const { return bm_.num_donors(); }
+  int32_t block_ref(int32_t block) const {
+    return (block >= 0 && block < bm_.num_blocks()) ? bm_.ref_count(block) : -1;
+  }
   bool has_work() const { return !running_.empty() || !waiting_.empty(); }
   void reset_prefix_cache();
   // Pooling rows whose embedding request was preempted in the last schedule() (it restarts
@@ -345,6 +377,11 @@ class Scheduler {
   bool ensure_blocks(Sequence* s, int32_t upto_tokens);
   void preempt(Sequence* s);
   void match_prefix(Sequence* s);
+  // blocks of `r` (planned in the step being built, ending at r_end tokens) that `s` can share
+  int32_t share_same_step(Sequence* s, const Sequence* r, int32_t r_end);
+  void match_partial(Sequence* s);
+  void count_cached(Sequence* s);
+  void drop_copy(Sequence* s);
   void register_full_blocks(Sequence* s);
   SeqOutput finish(Sequence* s, int32_t reason, double now);
   void free_seq(Sequence* s, bool keep_embed_slot = false);
@@ -360,6 +397,7 @@ class Scheduler {
     int32_t n;
     bool sample;
     int32_t end = 0;              // num_computed after this entry (its last token's position + 1)
+    int32_t keep = 1;             // tokens the alignment trim must leave: another entry reads their blocks
     int32_t score_rows = 0;       // scoring request: rows of the step this entry owns (its last tokens)
     bool spec = false;            // speculative continuation of a row sampling in the previous plan
     bool voided = false;          // the speculation failed: nothing of this entry is committed
@@ -389,6 +427,8 @@ class Scheduler {
   int64_t stat_prompt_tokens_ = 0, stat_cached_tokens_ = 0, stat_preemptions_ = 0, stat_steps_ = 0;
   int64_t stat_aligned_steps_ = 0;
   int64_t stat_prefix_defers_ = 0;
+  int64_t stat_partial_tokens_ = 0, stat_same_step_ = 0;
+  bool copies_ok_ = false;  // the buffer of the schedule() call in progress holds the copy list
   uint64_t prefix_key(const Sequence* s) const;
 };
 

@@ -78,6 +78,13 @@ class EngineConfig:
     kv_reserve_gb: float = 20.0  # HBM always left outside the KV pool (graphs, activations, workspaces)
     prefix_caching: bool = True
     dedup_inflight_prefix: bool = True  # requests wait for an identical prefix another request is prefilling
+    # a request whose prefix another request computes in this very step joins the step and reads
+    # those blocks instead of waiting a step for them (scheduler.h same_step_prefix)
+    same_step_prefix: bool = os.environ.get("PILOTTAI_PREFIX_SAME_STEP", "1") != "0"
+    # a prompt that leaves the cached prefix inside a 16-token block copies the common head of
+    # the best cached block instead of computing it (scheduler.h partial_block_reuse; the step
+    # graph's first kernel, csrc/ops/kv_copy.hip). TP = 1 only.
+    partial_block_reuse: bool = os.environ.get("PILOTTAI_PREFIX_PARTIAL", "1") != "0"
     # waiting embedding requests are admitted before waiting generation prompts (scheduler.h)
     embed_first: bool = os.environ.get("PILOTTAI_EMBED_FIRST", "1") != "0"
     split_decode: bool = True
@@ -305,6 +312,8 @@ class LLMEngine:
         self.buckets = sorted({b for b in buckets if b <= cfg.max_num_batched_tokens} |
                               {cfg.max_num_batched_tokens})
         small = [b for b in self.buckets if b <= self.model.DECODE_FUSED_MAX_T]
+        # the copy list travels in a region of its own, which TP followers do not receive
+        self._partial = bool(cfg.partial_block_reuse) and bool(cfg.prefix_caching) and self.tp.size == 1
         small_step = max(small) if (small and self.model.ATT_DECODE_WAVES == 8 and self.model.decode_packed) else 0
         self.sched = _runtime.Scheduler({
             "num_blocks": nb, "block_size": cfg.block_size, "max_num_seqs": cfg.max_num_seqs,
@@ -316,6 +325,8 @@ class LLMEngine:
             "prefill_split_keys": cfg.prefill_split_keys,
             "prefix_caching": cfg.prefix_caching, "split_decode": cfg.split_decode,
             "dedup_inflight_prefix": cfg.dedup_inflight_prefix,
+            "same_step_prefix": bool(cfg.same_step_prefix),
+            "partial_block_reuse": self._partial,
             "embed_first": bool(cfg.embed_first),
             "token_align": cfg.token_align, "align_slack": cfg.align_slack,
             "kv_heads": self.model.kv_local,
@@ -331,11 +342,11 @@ class LLMEngine:
         # one being scheduled); the device copy is stream-ordered behind the previous step
         self._async = bool(cfg.async_steps) and self.tp.size == 1
         nbuf = 2 if self._async else 1
-        self._host_metas = [torch.zeros(L["score_total"], dtype=torch.int32, pin_memory=pin) for _ in range(nbuf)]
+        self._host_metas = [torch.zeros(L["copy_total"], dtype=torch.int32, pin_memory=pin) for _ in range(nbuf)]
         self._host_meta = self._host_metas[0]
         self._host_ptr = self._host_meta.data_ptr()
         self._host_np = self._host_meta.numpy()
-        self._dev_meta = torch.zeros(L["score_total"], dtype=torch.int32, device=self.device) \
+        self._dev_meta = torch.zeros(L["copy_total"], dtype=torch.int32, device=self.device) \
             if (self.on_gpu or self._async) else self._host_meta
         # attention tickets: one per (sequence, KV head) for split decode rows, then -- only with
         # prefill_split_keys on -- one per (partial slot, KV head) for split prefill items
@@ -534,6 +545,8 @@ class LLMEngine:
         self._rep_n = sl("rep_n", ms)
         self._rep_tok = sl("rep_tok", L["rep_cap"])
         self._score_target = sl("score_target", ms)
+        self._n_copies = sl("n_copies", 1)
+        self._copy_list = sl("copy_list", 3 * ms)
 
     def _sync_masks(self) -> bool:
         reg = self.grammar.reg
@@ -570,6 +583,10 @@ class LLMEngine:
                             lp: bool = False, pen: bool = False, shape: bool = False, rep: bool = False,
                             score: bool = False):
         meta = self._meta_for(bucket, s_b, ns)
+        if self._partial:
+            # partial-block prefix hits: the cached heads go into the new blocks before any layer
+            # writes or reads KV (a step without copies: the kernel reads a zero count and exits)
+            ops.kv_copy(self.kv.k, self.kv.v, self._n_copies, self._copy_list)
         if self._async:  # pending tokens of rows that sampled in the previous step
             ops.patch_pending_ids(meta.input_ids[:bucket], self._sampled_dev)
         logits = self.model.forward(meta, self.kv, bucket, s_b, self._part_o, self._part_ml,
@@ -665,8 +682,9 @@ class LLMEngine:
         key = self._graph_key(bucket, trunc, embed, lp, pen, shape, rep, score)
         g = self._graphs.get(key)
         if g is None:
-            if shape or rep or score:  # their regions lie behind the copied prefix: keep the whole buffer
-                n_copy = self.L["score_total"]
+            # the regions of shaped / repetition / scoring rows and the copy list lie behind the
+            # copied prefix: keep the whole buffer
+            n_copy = self.L["copy_total"]
             saved = self._dev_meta[:n_copy].clone()
             pool = self._embed_pool.clone()
             samp = self._sampled_dev.clone()  # the previous step's tokens (pipelined mode)
@@ -695,6 +713,12 @@ class LLMEngine:
         a, b = self.L["score_target"], self.L["score_target"] + self.L["max_seqs"]
         self._dev_meta[a:b].copy_(hm[a:b], non_blocking=self.on_gpu)
 
+    def _copy_copies(self, hm: torch.Tensor, n: int):
+        """Host -> device copy of the `n` partial-block copy triples of a step that has some (the
+        count itself lies in the header every step copies)."""
+        a = self.L["copy_list"]
+        self._dev_meta[a:a + 3 * n].copy_(hm[a:a + 3 * n], non_blocking=self.on_gpu)
+
     def _copy_repetition(self, hm: torch.Tensor, n_tok: int):
         """Host -> device copy of the repetition regions of a step with such a row: the per-row
         words and the `n_tok` token words in use, one piece."""
@@ -707,7 +731,7 @@ class LLMEngine:
     def _dummy_meta(self):
         """A metadata state under which a forward touches no KV and no attention item."""
         L = self.L
-        d = torch.zeros(L["score_total"], dtype=torch.int32)
+        d = torch.zeros(L["copy_total"], dtype=torch.int32)  # n_copies = 0: the copy kernel touches nothing
         d[L["slots"]:L["slots"] + L["max_tokens"]] = -1
         d[L["embed_rows"]:L["embed_rows"] + L["max_tokens"]] = L["max_seqs"]
         d[L["pen_slot"]:L["pen_slot"] + L["max_seqs"]] = -1  # the penalty pass touches nothing
@@ -1307,6 +1331,9 @@ class LLMEngine:
                 self._copy_repetition(self._host_meta, rep >> 1)
             if score:
                 self._copy_scoring(self._host_meta)
+            ncp = int(self._host_np[L["n_copies"]])
+            if ncp:
+                self._copy_copies(self._host_meta, ncp)
         if self.tp.size > 1:
             self._tp_send(_OP_STEP, T, ns, nsamp, bucket, int(masks_changed), n_copy, int(trunc), int(embed))
             if masks_changed:
@@ -1404,6 +1431,9 @@ class LLMEngine:
             self._copy_shaping(hm, shape - 1)
         if score:
             self._copy_scoring(hm)
+        ncp = int(hm.numpy()[L["n_copies"]])
+        if ncp:
+            self._copy_copies(hm, ncp)
         with torch.inference_mode(), trace_range("engine.forward"):
             self._run(bucket, ns, trunc, n_copy, embed, lp, shape=shape > 0, score=score)
         if self._step_listeners:
@@ -1536,6 +1566,7 @@ class LLMEngine:
             "prompt_tokens": s.total_prompt_tokens, "prefix_cache_hit_tokens": s.total_cached_tokens,
             "preemptions": s.total_preemptions, "graphs": len(self._graphs), "aligned_steps": s.aligned_steps,
             "prefix_defers": s.prefix_defers,
+            "partial_hit_tokens": s.partial_hit_tokens, "same_step_shares": s.same_step_shares,
             "spec_rows": s.spec_rows, "spec_voided": s.spec_voided,
             "kv_cache_gb": self.kv.k.numel() * 2 * 2 / 2**30,
             "weights_gb": self.model.weight_bytes() / 2**30,

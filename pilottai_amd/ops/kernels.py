@@ -124,6 +124,18 @@ def rope_cache(q_out, k_cache, v_cache, qkv, positions, slot_mapping, cos_sin, H
     return q_out
 
 
+def kv_copy(k_cache, v_cache, n_copies, copies) -> None:
+    """Partial-block prefix reuse (csrc/ops/kv_copy.hip): for each of the first `n_copies[0]`
+    (donor block, new block, j) triples of `copies`, copy the first j key slots of the donor's
+    K and V pages to the new block, in every layer and KV head. `k_cache` is
+    [layers, blocks, KV, 16, 16, 8], `v_cache` [layers, blocks, KV, 128, 16]; the count and the
+    triples are int32 tensors on the caches' device (graph-capturable: a fixed launch shape)."""
+    if _on_gpu(k_cache):
+        require_native().kv_copy(k_cache, v_cache, n_copies, copies)
+        return
+    ref.kv_copy(k_cache, v_cache, n_copies, copies)
+
+
 def paged_attention(out, part_o, part_ml, q, k_cache, v_cache, items, n_items, counters,
                     q_start, q_len, ctx_len, block_table, scale: float, num_seqs: Optional[int] = None,
                     part_size: Optional[torch.Tensor] = None, waves: int = 4):

@@ -100,6 +100,19 @@ def rope_cache(q_out, k_cache, v_cache, qkv, positions, slot_mapping, cos_sin, H
         v_cache[b, :, :, o] = v[t]
 
 
+def kv_copy(k_cache, v_cache, n_copies, copies):
+    """k_cache [layers, blocks, KV, 16, block, 8], v_cache [layers, blocks, KV, 128, block]: the
+    first j slots of block `src` go to block `dst` for each of the first n_copies[0] triples."""
+    blk = k_cache.shape[4]
+    tri = copies.reshape(-1)[: 3 * int(n_copies.reshape(-1)[0])].reshape(-1, 3).tolist()
+    for src, dst, j in tri:
+        j = min(int(j), blk)
+        if j <= 0 or src == dst:
+            continue
+        k_cache[:, dst, :, :, :j, :] = k_cache[:, src, :, :, :j, :]
+        v_cache[:, dst, :, :, :j] = v_cache[:, src, :, :, :j]
+
+
 def paged_attention(q, k_cache, v_cache, q_start, q_len, ctx_len, block_table, scale):
     """q [T, H, 128]; returns out [T, H, 128] (fp32 math, causal within context)."""
     T, H, hd = q.shape
