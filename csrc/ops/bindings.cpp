@@ -28,6 +28,13 @@ int pa_sample(int* out_tokens, float* out_keys, float* workspace, const void* lo
               int V, int ld, int vocab_offset, const float* temperature, const int* mask_class,
               const uint32_t* class_masks, int mask_words, const int64_t* seeds,
               const int* offsets, const int* forced, const float* tau, hipStream_t st);
+int pa_sample_partials(float* workspace, const void* logits, int rows, int V, int ld, int vocab_offset,
+                       const float* temperature, const int* mask_class, const uint32_t* class_masks,
+                       int mask_words, const int64_t* seeds, const int* offsets, const float* tau,
+                       hipStream_t st);
+int pa_spec_verify(int* out_tokens, int* accept_len, const float* part_k, const int* part_i, const int* forced,
+                   const int* input_ids, int n_ids, const int* logit_rows, const int* run_first,
+                   const int* run_len, int rows, int nchunk, hipStream_t st);
 int pa_logprob_workspace_floats(int rows, int V);
 int pa_token_logprobs(float* out_lp, int out_stride, int* top_ids, float* top_lp, int top_stride, float* workspace,
                       const void* logits, int rows, int V, int ld, const int* tokens, const int* lp_n,
@@ -717,6 +724,72 @@ void sample(at::Tensor out_tokens, c10::optional<at::Tensor> out_keys, at::Tenso
            "sample");
 }
 
+// The sampler's chunk pass alone (sampling.hip): fills the workspace's [rows, nchunk] partial keys
+// and ids; spec_verify() merges them. Same checks as sample().
+void sample_partials(at::Tensor workspace, at::Tensor logits, int64_t vocab_offset, at::Tensor temperature,
+                     at::Tensor mask_class, at::Tensor class_masks, at::Tensor seeds, at::Tensor offsets,
+                     c10::optional<at::Tensor> tau) {
+  check_gpu(workspace, "workspace"); check_gpu(temperature, "temperature"); check_gpu(mask_class, "mask_class");
+  check_gpu(class_masks, "class_masks"); check_gpu(seeds, "seeds"); check_gpu(offsets, "offsets");
+  TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.stride(1) == 1,
+              "logits must be a 2-D GPU tensor with unit inner stride");
+  check_dtype(logits, at::kBFloat16, "logits"); check_dtype(workspace, at::kFloat, "workspace");
+  check_dtype(temperature, at::kFloat, "temperature"); check_dtype(mask_class, at::kInt, "mask_class");
+  check_dtype(class_masks, at::kInt, "class_masks"); check_dtype(seeds, at::kLong, "seeds");
+  check_dtype(offsets, at::kInt, "offsets");
+  const int rows = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(temperature.numel() >= rows && mask_class.numel() >= rows && seeds.numel() >= rows &&
+                  offsets.numel() >= rows,
+              "per-row sampling parameter tensors too short");
+  TORCH_CHECK(workspace.is_contiguous() && workspace.numel() >= pa_sample_workspace_floats(rows, V),
+              "sample workspace too small");
+  TORCH_CHECK(class_masks.dim() == 2, "class_masks must be [classes, words]");
+  TORCH_CHECK(class_masks.size(1) * 32 >= vocab_offset + V, "class_masks too narrow for vocab");
+  const float* tp = nullptr;
+  if (tau.has_value()) {
+    check_gpu(*tau, "tau"); check_dtype(*tau, at::kFloat, "tau");
+    TORCH_CHECK(tau->numel() >= rows, "tau too short");
+    tp = tau->data_ptr<float>();
+  }
+  check_rc(pa_sample_partials(workspace.data_ptr<float>(), logits.data_ptr(), rows, V, logits.stride(0),
+                              vocab_offset, temperature.data_ptr<float>(), mask_class.data_ptr<int>(),
+                              reinterpret_cast<const uint32_t*>(class_masks.data_ptr<int>()),
+                              class_masks.size(1), seeds.data_ptr<int64_t>(), offsets.data_ptr<int>(), tp,
+                              cur_stream()),
+           "sample_partials");
+}
+
+// Final merge + draft verification of a draft step (spec_verify.hip). part_k fp32 / part_i int32
+// [rows, nchunk] contiguous; forced, logit_rows, run_first, run_len, out_tokens, accept_len hold
+// at least `rows` int32 words; input_ids is the step's token ids.
+void spec_verify(at::Tensor out_tokens, at::Tensor accept_len, at::Tensor part_k, at::Tensor part_i,
+                 at::Tensor forced, at::Tensor input_ids, at::Tensor logit_rows, at::Tensor run_first,
+                 at::Tensor run_len) {
+  check_gpu(out_tokens, "out_tokens"); check_gpu(accept_len, "accept_len"); check_gpu(part_k, "part_k");
+  check_gpu(part_i, "part_i"); check_gpu(forced, "forced"); check_gpu(input_ids, "input_ids");
+  check_gpu(logit_rows, "logit_rows"); check_gpu(run_first, "run_first"); check_gpu(run_len, "run_len");
+  check_dtype(out_tokens, at::kInt, "out_tokens"); check_dtype(accept_len, at::kInt, "accept_len");
+  check_dtype(part_k, at::kFloat, "part_k"); check_dtype(part_i, at::kInt, "part_i");
+  check_dtype(forced, at::kInt, "forced"); check_dtype(input_ids, at::kInt, "input_ids");
+  check_dtype(logit_rows, at::kInt, "logit_rows"); check_dtype(run_first, at::kInt, "run_first");
+  check_dtype(run_len, at::kInt, "run_len");
+  TORCH_CHECK(part_k.dim() == 2 && part_i.dim() == 2 && part_k.sizes() == part_i.sizes() &&
+                  part_k.is_contiguous() && part_i.is_contiguous() && part_k.size(1) >= 1,
+              "part_k / part_i: contiguous [rows, nchunk] tensors of one shape");
+  const int64_t rows = part_k.size(0), nchunk = part_k.size(1);
+  TORCH_CHECK(rows * nchunk < (int64_t(1) << 31), "spec_verify: too many partials");
+  for (const at::Tensor* t : {&out_tokens, &accept_len, &forced, &logit_rows, &run_first, &run_len})
+    TORCH_CHECK(t->dim() == 1 && t->is_contiguous() && t->numel() >= rows,
+                "spec_verify: per-row tensors must be contiguous 1-D with at least `rows` entries");
+  TORCH_CHECK(input_ids.dim() == 1 && input_ids.is_contiguous() && input_ids.numel() < (int64_t(1) << 31),
+              "input_ids: contiguous 1-D int32 tensor");
+  check_rc(pa_spec_verify(out_tokens.data_ptr<int>(), accept_len.data_ptr<int>(), part_k.data_ptr<float>(),
+                          part_i.data_ptr<int>(), forced.data_ptr<int>(), input_ids.data_ptr<int>(),
+                          (int)input_ids.numel(), logit_rows.data_ptr<int>(), run_first.data_ptr<int>(),
+                          run_len.data_ptr<int>(), (int)rows, (int)nchunk, cur_stream()),
+           "spec_verify");
+}
+
 int64_t logprob_workspace_floats(int64_t rows, int64_t V) {
   return pa_logprob_workspace_floats(rows, V);
 }
@@ -1400,6 +1473,12 @@ PYBIND11_MODULE(_C, m) {
   m.def("sample_workspace_floats", &sample_workspace_floats);
   m.def("patch_pending_ids", &patch_pending_ids);
   m.def("kv_copy", &kv_copy);
+  m.def("sample_partials", &sample_partials, py::arg("workspace"), py::arg("logits"), py::arg("vocab_offset"),
+        py::arg("temperature"), py::arg("mask_class"), py::arg("class_masks"), py::arg("seeds"),
+        py::arg("offsets"), py::arg("tau") = py::none());
+  m.def("spec_verify", &spec_verify, py::arg("out_tokens"), py::arg("accept_len"), py::arg("part_k"),
+        py::arg("part_i"), py::arg("forced"), py::arg("input_ids"), py::arg("logit_rows"),
+        py::arg("run_first"), py::arg("run_len"));
   m.def("sample", &sample, py::arg("out_tokens"), py::arg("out_keys"), py::arg("workspace"),
         py::arg("logits"), py::arg("vocab_offset"), py::arg("temperature"), py::arg("mask_class"),
         py::arg("class_masks"), py::arg("seeds"), py::arg("offsets"), py::arg("forced"),

@@ -414,6 +414,23 @@ extern "C" int pa_sample(int* out_tokens, float* out_keys, float* workspace, con
   return (int)hipGetLastError();
 }
 
+// The chunk pass of pa_sample alone: draft steps (spec_verify.hip) merge the partials and verify
+// the draft in one launch of their own instead of sample_final_kernel. Same workspace layout.
+extern "C" int pa_sample_partials(float* workspace, const void* logits, int rows, int V, int ld,
+                                  int vocab_offset, const float* temperature, const int* mask_class,
+                                  const uint32_t* class_masks, int mask_words, const int64_t* seeds,
+                                  const int* offsets, const float* tau, hipStream_t st) {
+  if (rows <= 0) return 0;
+  if (V % 8 != 0 || ld % 8 != 0) return -1;
+  const int nchunk = (V + pa::SMP_CHUNK - 1) / pa::SMP_CHUNK;
+  float* pk = workspace;
+  int* pi = reinterpret_cast<int*>(workspace + (size_t)rows * nchunk);
+  hipLaunchKernelGGL(pa::sample_chunk_kernel, dim3(nchunk, rows), dim3(256), 0, st, pk, pi,
+                     (const pa::bf16*)logits, V, ld, vocab_offset, temperature, mask_class,
+                     class_masks, mask_words, seeds, offsets, nchunk, tau);
+  return (int)hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------
 // Per-token log-probabilities. The sampler never normalises (Gumbel-max), so this is a pass of
 // its own over the logits, run behind pa_sample on the same stream: the distribution is

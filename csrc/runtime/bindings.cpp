@@ -261,6 +261,7 @@ PYBIND11_MODULE(_runtime, m) {
         d["rep_tok"] = L.rep_tok; d["rep_cap"] = L.rep_cap; d["rep_total"] = L.rep_total;
         d["score_target"] = L.score_target; d["score_total"] = L.score_total;
         d["n_copies"] = L.n_copies; d["copy_list"] = L.copy_list; d["copy_total"] = L.copy_total;
+        d["run_first"] = L.run_first; d["run_len"] = L.run_len; d["spec_total"] = L.spec_total;
         d["total"] = L.total;
         return d;
       })
@@ -271,11 +272,13 @@ PYBIND11_MODULE(_runtime, m) {
               float top_p, bool embed, bool embed_last, int32_t logprobs, float presence_penalty,
               float frequency_penalty, const std::vector<std::pair<int32_t, float>>& logit_bias,
               float min_p, float ln_min_p, float repetition_penalty, float inv_repetition_penalty,
-              int32_t score_from) {
+              int32_t score_from, const std::vector<int32_t>& prediction, bool prompt_lookup,
+              int32_t draft_len) {
              s.add_request(id, prompt, temperature, max_tokens, seed, ignore_eos, stop_ids,
                            make_grammar(grammar), top_k, top_p, embed, embed_last, logprobs,
                            presence_penalty, frequency_penalty, logit_bias, min_p, ln_min_p,
-                           repetition_penalty, inv_repetition_penalty, score_from);
+                           repetition_penalty, inv_repetition_penalty, score_from, prediction,
+                           prompt_lookup, draft_len);
            },
            py::arg("id"), py::arg("prompt"), py::arg("temperature"), py::arg("max_tokens"),
            py::arg("seed"), py::arg("ignore_eos"), py::arg("stop_ids"), py::arg("grammar"),
@@ -284,7 +287,9 @@ PYBIND11_MODULE(_runtime, m) {
            py::arg("frequency_penalty") = 0.0f,
            py::arg("logit_bias") = std::vector<std::pair<int32_t, float>>{}, py::arg("min_p") = 0.0f,
            py::arg("ln_min_p") = 0.0f, py::arg("repetition_penalty") = 1.0f,
-           py::arg("inv_repetition_penalty") = 0.0f, py::arg("score_from") = -1)
+           py::arg("inv_repetition_penalty") = 0.0f, py::arg("score_from") = -1,
+           py::arg("prediction") = std::vector<int32_t>{}, py::arg("prompt_lookup") = false,
+           py::arg("draft_len") = 0)
       // words: the buffer's size in 32-bit words (0 = not stated: steps of requests with a
       // repetition penalty, which write behind layout()["total"], are then refused)
       .def("schedule", [](Scheduler& s, uintptr_t buf, int32_t words) {
@@ -295,16 +300,34 @@ PYBIND11_MODULE(_runtime, m) {
       // logprob, 20 ids, 20 logprobs), 0 = the step computed none
       // scores: address of the step's ScoreRecord array (42 words per row: logprob, rank, 20 ids,
       // 20 logprobs; indexed by row like `sampled`), 0 = the step computed none
-      .def("commit", [](Scheduler& s, uintptr_t sampled, int32_t n, uintptr_t logprobs, uintptr_t scores) {
+      // accept_len: address of the step's acceptance lengths (one int32 per row, indexed like
+      // `sampled`; csrc/ops/spec_verify.hip), 0 = every run commits one token
+      .def("commit", [](Scheduler& s, uintptr_t sampled, int32_t n, uintptr_t logprobs, uintptr_t scores,
+                        uintptr_t accept_len) {
         std::vector<SeqOutput> outs;
         {
           py::gil_scoped_release nogil;
           outs = s.commit(reinterpret_cast<const int32_t*>(sampled), n,
                           reinterpret_cast<const LogprobRecord*>(logprobs),
-                          reinterpret_cast<const ScoreRecord*>(scores));
+                          reinterpret_cast<const ScoreRecord*>(scores),
+                          reinterpret_cast<const int32_t*>(accept_len));
         }
         return outputs_to_py(outs);
-      }, py::arg("sampled"), py::arg("n"), py::arg("logprobs") = 0, py::arg("scores") = 0)
+      }, py::arg("sampled"), py::arg("n"), py::arg("logprobs") = 0, py::arg("scores") = 0,
+         py::arg("accept_len") = 0)
+      .def_property_readonly_static("COUNTS9_SPEC_BIT", [](const py::object&) { return (int)COUNTS9_SPEC_BIT; })
+      .def_property_readonly_static("MAX_DRAFT_LEN", [](const py::object&) { return (int)MAX_DRAFT_LEN; })
+      .def_property_readonly("spec_draft_tokens", &Scheduler::spec_draft_tokens)
+      .def_property_readonly("spec_accepted_tokens", &Scheduler::spec_accepted_tokens)
+      .def_property_readonly("spec_draft_steps", &Scheduler::spec_draft_steps)
+      .def_property_readonly("spec_runs_full", &Scheduler::spec_runs_full)
+      // [(id, proposed, accepted, prediction_matched)] of the drafting requests finished since the last call
+      .def("take_draft_counts", [](Scheduler& s) {
+        py::list l;
+        for (const auto& c : s.take_draft_counts()) l.append(py::make_tuple(c.id, c.proposed, c.accepted, c.matched));
+        return l;
+      })
+      .def("planned_draft", &Scheduler::planned_draft)
       .def_property_readonly_static("LOGPROB_RECORD_WORDS",
                                     [](const py::object&) { return (int)(sizeof(LogprobRecord) / 4); })
       .def_property_readonly_static("SCORE_RECORD_WORDS",

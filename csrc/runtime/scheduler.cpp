@@ -97,6 +97,9 @@ Scheduler::Scheduler(const SchedulerConfig& cfg)
   L.n_copies = L.n_items + 1;  // a word of the header's padding: every step copies it
   L.copy_list = take(3 * L.max_seqs);
   L.copy_total = o;
+  L.run_first = take(L.max_seqs);
+  L.run_len = take(L.max_seqs);
+  L.spec_total = o;
   for (int32_t r = L.max_seqs; r-- > 0;) embed_free_.push_back(r);
   for (int32_t r = std::max(0, std::min(cfg.max_num_seqs, cfg.penalty_slots)); r-- > 0;) pen_free_.push_back(r);
 }
@@ -108,7 +111,20 @@ void Scheduler::add_request(int64_t id, std::vector<int32_t> prompt, float tempe
                             float presence_penalty, float frequency_penalty,
                             std::vector<std::pair<int32_t, float>> logit_bias, float min_p,
                             float ln_min_p, float repetition_penalty, float inv_repetition_penalty,
-                            int32_t score_from) {
+                            int32_t score_from, std::vector<int32_t> prediction, bool prompt_lookup,
+                            int32_t draft_len) {
+  draft_len = std::max(0, std::min(draft_len, MAX_DRAFT_LEN));
+  const bool drafting = draft_len > 0 && (!prediction.empty() || prompt_lookup);
+  if (drafting) {
+    // a draft row samples before the tokens in front of it are known to be real: state kept per
+    // committed token (penalty counts, seen sets) and records per token cannot follow that
+    if (embed || score_from != -1 || logprobs >= 0 || presence_penalty != 0.f || frequency_penalty != 0.f ||
+        (repetition_penalty != 1.f && repetition_penalty > 0.f))
+      throw std::invalid_argument("scheduler: a drafting request takes no embed, score_from, logprobs, "
+                                  "presence / frequency penalty or repetition_penalty");
+    for (int32_t t : prediction)
+      if (t < 0) throw std::invalid_argument("scheduler: prediction token ids must be >= 0");
+  }
   if (score_from != -1) {
     // nothing of a scoring request may be dropped or changed silently: its records are
     // per prompt position
@@ -178,6 +194,12 @@ void Scheduler::add_request(int64_t id, std::vector<int32_t> prompt, float tempe
     s->inv_repetition_penalty = (std::isfinite(inv_repetition_penalty) && inv_repetition_penalty > 0.f)
                                     ? inv_repetition_penalty : (float)(1.0 / (double)repetition_penalty);
   }
+  if (drafting) {
+    s->prediction = std::move(prediction);
+    s->prompt_lookup = prompt_lookup;
+    s->draft_len = draft_len;
+    ++draft_live_;
+  }
   s->arrival = arrival_counter_++;
   // a grammar that starts with forced text (e.g. '{"key": ') is jump-forwarded into the prompt
   if (s->grammar) {
@@ -189,6 +211,7 @@ void Scheduler::add_request(int64_t id, std::vector<int32_t> prompt, float tempe
       for (int32_t j = 0; j < k; ++j)
         s->lp_records.push_back(forced_record(s->tokens[s->prompt_len + j], s->logprobs));
   }
+  follow_prediction(s.get(), (size_t)s->prompt_len);  // the forced head of the reply
   Sequence* raw = s.get();
   seqs_.emplace(id, std::move(s));
   waiting_.push_back(raw);
@@ -340,6 +363,71 @@ void Scheduler::register_full_blocks(Sequence* s) {
   }
 }
 
+// Tokens tokens[from:] were just committed: the prediction cursor follows them while they are
+// the prediction's own next tokens, and loses its alignment at the first one that is not.
+int32_t Scheduler::follow_prediction(Sequence* s, size_t from) {
+  int32_t matched = 0;
+  if (s->prediction.empty()) return matched;
+  for (size_t i = from; i < s->tokens.size() && s->pred_synced; ++i) {
+    if (s->pred_c < (int32_t)s->prediction.size() && s->prediction[s->pred_c] == s->tokens[i]) {
+      ++s->pred_c;
+      ++matched;
+    } else {
+      // the cursor steps over the token that failed, so the resync looks behind it: a reply of
+      // one repeated token would otherwise resync onto the same wrong token for ever
+      s->pred_synced = false;
+      if (s->pred_c < (int32_t)s->prediction.size()) ++s->pred_c;
+    }
+  }
+  return matched;
+}
+
+// The draft of a decode row, t = the request's tokens so far:
+//   prediction  with the cursor c aligned (the tokens committed last were the prediction's):
+//               prediction[c : c + k]. Otherwise resync: for n = 4, 3, 2 the first i >= c with
+//               prediction[i - n : i] == t[-n:] becomes c. No n matches: the prediction proposes
+//               nothing and c stays (it never moves back; follow_prediction has put it behind the
+//               prediction token that failed).
+//   lookup      (prompt_lookup, and the prediction proposed nothing) for n = 4, 3, 2 the latest
+//               i <= len(t) - 1 with t[i - n : i] == t[-n:]: t[i : i + k], cut at the end of t.
+std::vector<int32_t> Scheduler::propose(Sequence* s, int32_t k, bool* from_prediction) const {
+  std::vector<int32_t> out;
+  *from_prediction = false;
+  if (k <= 0) return out;
+  const std::vector<int32_t>& t = s->tokens;
+  const std::vector<int32_t>& P = s->prediction;
+  const int32_t len = (int32_t)t.size(), plen = (int32_t)P.size();
+  if (plen > 0) {
+    if (!s->pred_synced) {
+      for (int32_t n = 4; n >= 2 && !s->pred_synced; --n) {
+        if (len < n) continue;
+        for (int32_t i = std::max(s->pred_c, n); i < plen; ++i)
+          if (std::equal(P.begin() + (i - n), P.begin() + i, t.end() - n)) {
+            s->pred_c = i;
+            s->pred_synced = true;
+            break;
+          }
+      }
+    }
+    if (s->pred_synced && s->pred_c < plen) {
+      out.assign(P.begin() + s->pred_c, P.begin() + std::min(plen, s->pred_c + k));
+      *from_prediction = true;
+      return out;
+    }
+  }
+  if (s->prompt_lookup) {
+    for (int32_t n = 4; n >= 2; --n) {
+      if (len <= n) continue;
+      for (int32_t i = len - 1; i >= n; --i)
+        if (std::equal(t.begin() + (i - n), t.begin() + i, t.end() - n)) {
+          out.assign(t.begin() + i, t.begin() + std::min(len, i + k));
+          return out;
+        }
+    }
+  }
+  return out;
+}
+
 int32_t Scheduler::schedule(int32_t* buf, int32_t buf_words) {
   const StepLayout& L = lay_;
   const int32_t B = cfg_.block_size;
@@ -350,6 +438,7 @@ int32_t Scheduler::schedule(int32_t* buf, int32_t buf_words) {
     throw std::invalid_argument("scheduler: a scoring request needs a step buffer of "
                                 "layout().score_total words, stated as schedule()'s second argument");
   copies_ok_ = buf_words >= L.copy_total;
+  drafts_ok_ = buf_words >= L.spec_total && plans_.empty();
   last_plan_.clear();
   // rows of the step (sampling rows + scoring rows) never exceed max_num_seqs. A scoring request
   // can own many: every running sequence that may sample keeps one in reserve, so decode rows are
@@ -360,8 +449,10 @@ int32_t Scheduler::schedule(int32_t* buf, int32_t buf_words) {
   // before it (a scoring chunk is cut a little harder than needed, never the other way round);
   // one still more than a step's tokens away from its last prompt token cannot sample and does
   // not count. All of it is skipped while no scoring request is alive (score_live_).
+  // Draft rows (a drafting request's rows beyond its first) are budgeted the same way and
+  // counted in score_rows_used: plain decode rows are served first, a draft is cut to what is left.
   int32_t rows_reserved = 0, score_rows_used = 0;
-  const bool budget_rows = score_live_ > 0;
+  const bool budget_rows = score_live_ > 0 || (drafts_ok_ && draft_live_ > 0);
   if (budget_rows)
     for (const Sequence* r : running_)
       if (r->running && !r->embed && !r->scoring() &&
@@ -444,11 +535,77 @@ int32_t Scheduler::schedule(int32_t* buf, int32_t buf_words) {
       if (s->inflight == 0) preempt(s);
       continue;
     }
-    last_plan_.push_back({s, n, samples(s, n)});
+    Planned e{s, n, samples(s, n)};
     tok_budget -= n;
+    if (e.sample && drafts_ok_ && s->drafting()) {
+      // k: the smallest of draft_len, the tokens the request may still generate minus the one
+      // the last row samples, the rows and tokens the step has left, and the free blocks beyond
+      // what the running sequences behind this one need for their own next tokens and the
+      // admission watermark -- a draft never preempts anybody
+      int32_t k = std::min(s->draft_len, s->max_tokens - s->num_generated - 1);
+      k = std::min(k, cfg_.max_model_len - (int32_t)s->tokens.size() - 1);
+      k = std::min(k, cfg_.max_num_seqs - rows_reserved - score_rows_used);
+      k = std::min(k, tok_budget);
+      if (k > 0) {
+        int32_t others = 0;
+        for (size_t j = i + 1; j < running_.size(); ++j) {
+          const Sequence* r = running_[j];
+          if (r->running) others += std::max(0, (r->compute_len() + B - 1) / B - (int32_t)r->blocks.size());
+        }
+        const int32_t spare = bm_.num_free() - others - std::max(1, cfg_.num_blocks / 100);
+        k = std::min(k, ((int32_t)s->blocks.size() + std::max(0, spare)) * B - (s->num_computed + n));
+      }
+      if (k > 0) e.draft = propose(s, k, &e.draft_pred);
+      if (!e.draft.empty()) {
+        // the grammar runs ahead along the draft on a copy of the cursor: row j samples in the
+        // state behind j draft tokens. A forced token that differs from the draft ends the draft
+        // (that row emits the forced token, the correction, at no cost); so does a draft token
+        // that would end the reply (the row in front of it samples it, and the commit finishes
+        // the request as ever). A draft token the mask does not allow needs no care: advance_at
+        // only compares it with the segment's closing tokens, and the row that verifies it can
+        // never sample it, so every row behind it is dropped.
+        int32_t cls = -1, forced = -1;
+        if (s->grammar) {
+          const Grammar& g = *s->grammar;
+          Grammar::Cursor c = g.cursor();
+          size_t j = 0;
+          for (; j < e.draft.size(); ++j) {
+            g.next_at(c, &cls, &forced);
+            e.row_gram.emplace_back(cls, forced);
+            if (forced >= 0 && forced != e.draft[j]) break;
+            Grammar::Cursor c2 = c;
+            g.advance_at(c2, e.draft[j]);
+            if (g.done_at(c2)) break;
+            c = c2;
+          }
+          if (j < e.draft.size()) {
+            e.draft.resize(j);  // row j (already listed) is the run's last
+          } else {
+            g.next_at(c, &cls, &forced);
+            e.row_gram.emplace_back(cls, forced);
+          }
+        } else {
+          e.row_gram.assign(e.draft.size() + 1, {-1, -1});
+        }
+      }
+      if (!e.draft.empty()) {
+        const int32_t k2 = (int32_t)e.draft.size();
+        if (ensure_blocks(s, s->num_computed + n + k2)) {
+          e.n = n + k2;
+          tok_budget -= k2;
+          score_rows_used += k2;
+          s->draft_proposed += k2;
+          stat_draft_tokens_ += k2;
+        } else {  // cannot happen: k was cut to the free blocks
+          e.draft.clear();
+        }
+      }
+      if (e.draft.empty()) e.row_gram.clear();
+    }
     pair_used += pairs;
     rep_used += reps;
     score_rows_used += score_rows_of(s, s->num_computed, n);
+    last_plan_.push_back(std::move(e));
   }
   running_.erase(std::remove_if(running_.begin(), running_.end(),
                                 [](Sequence* s) { return !s->running; }),
@@ -607,12 +764,12 @@ int32_t Scheduler::schedule(int32_t* buf, int32_t buf_words) {
     const int32_t r = T % cfg_.token_align;
     if (T > cfg_.token_align && r > 0 && r <= cfg_.align_slack) {
       int32_t cap = 0;
-      for (const Planned& p : last_plan_) cap += p.spec ? 0 : std::max(0, p.n - p.keep);
+      for (const Planned& p : last_plan_) cap += (p.spec || !p.draft.empty()) ? 0 : std::max(0, p.n - p.keep);
       if (cap >= r) {
         int32_t left = r;
         for (size_t i = last_plan_.size(); i-- > 0 && left > 0;) {
           Planned& p = last_plan_[i];
-          if (p.spec) continue;
+          if (p.spec || !p.draft.empty()) continue;
           const int32_t cut = std::min(left, std::max(0, p.n - p.keep));
           p.n -= cut;
           left -= cut;
@@ -695,6 +852,11 @@ int32_t Scheduler::schedule(int32_t* buf, int32_t buf_words) {
 
   int32_t* cpl = buf + L.copy_list;
   int32_t ncopy = 0;
+  // draft steps: the run regions are written only when a planned entry owns draft rows
+  bool any_draft = false;
+  for (const Planned& p : last_plan_) any_draft = any_draft || !p.draft.empty();
+  int32_t* rfi = buf + L.run_first;
+  int32_t* rln = buf + L.run_len;
 
   int32_t T = 0, ns = 0, nsamp = 0, nit = 0, nparted = 0, pslot = 0;
   // decode partition size: with few decode rows, 256-key flash-decoding partitions
@@ -800,7 +962,9 @@ int32_t Scheduler::schedule(int32_t* buf, int32_t buf_words) {
       const int32_t ppos = c0 + j;
       // speculative entry: the pending token comes from the in-flight step's sampled row
       // src_idx (the device patches -(src_idx + 1) before the embedding lookup)
-      ids[T + j] = !p.spec ? s->tokens[ppos] : (j == 0 ? -(p.src_idx + 1) : p.run[j - 1]);
+      const int32_t nreal = n - (int32_t)p.draft.size();  // the tokens behind them are the draft
+      ids[T + j] = p.spec ? (j == 0 ? -(p.src_idx + 1) : p.run[j - 1])
+                          : (j < nreal ? s->tokens[ppos] : p.draft[j - nreal]);
       pos[T + j] = ppos;
       slots[T + j] = s->blocks[ppos / B] * B + ppos % B;
       // last-token pooling: only the prompt's final token feeds the request's pooling row
@@ -821,18 +985,33 @@ int32_t Scheduler::schedule(int32_t* buf, int32_t buf_words) {
       ++ncopy;
       drop_copy(s);
     }
-    if (p.sample) {
-      lr[nsamp] = T + n - 1;
+    // a draft entry owns 1 + k rows, one per token from the last real one on: row r samples the
+    // token at position ctx - k + r from the logits of the token in front of it
+    const int32_t kd = (int32_t)p.draft.size();
+    const int32_t run0 = nsamp;
+    for (int32_t r = 0; p.sample && r <= kd; ++r) {
+      if (nsamp >= L.max_seqs)  // the planning above budgeted the rows
+        throw std::logic_error("scheduler: sampling rows overflow max_num_seqs");
+      lr[nsamp] = T + n - 1 - kd + r;
       int32_t cls = -1, forced = -1;
-      if (s->grammar) {
+      if (kd > 0) {
+        cls = p.row_gram[r].first;
+        forced = p.row_gram[r].second;
+      } else if (s->grammar) {
         if (p.spec) s->grammar->next_at(p.cur, &cls, &forced);
         else s->grammar->next(&cls, &forced);
       }
       mc[nsamp] = cls;
       fc[nsamp] = forced;
-      off[nsamp] = ctx;  // the sampled token's position (= tokens.size() for a known row)
-      s->pend_plan = plan_id;
-      s->pend_idx = nsamp;
+      off[nsamp] = ctx - kd + r;  // the sampled token's position (= tokens.size() for a known row)
+      if (r == 0) {
+        s->pend_plan = plan_id;
+        s->pend_idx = nsamp;
+      }
+      if (any_draft) {
+        rfi[nsamp] = run0;
+        rln[nsamp] = kd + 1;
+      }
       temp[nsamp] = s->temperature;
       tk[nsamp] = s->top_k;
       tp[nsamp] = s->top_p;
@@ -944,6 +1123,10 @@ int32_t Scheduler::schedule(int32_t* buf, int32_t buf_words) {
         bst[nsamp] = nbias;
         bnn[nsamp] = 0;
         bmp[nsamp] = bln[nsamp] = 0.f;
+      }
+      if (any_draft) {
+        rfi[nsamp] = nsamp;
+        rln[nsamp] = 1;
       }
       ++nsamp;
     }
@@ -1063,6 +1246,14 @@ int32_t Scheduler::schedule(int32_t* buf, int32_t buf_words) {
   // ... a row with a repetition penalty (repetition pass): bit 1, the rep_tok words in use above it
   if (nrep > 0) counts[9] |= 2 | (nreptok << 2);
   if (any_score) counts[9] |= COUNTS9_SCORE_BIT;  // ... scoring rows (scoring pass): bit 30
+  if (any_draft) {  // ... draft rows (the acceptance pass instead of the sampler's final merge): bit 29
+    counts[9] |= COUNTS9_SPEC_BIT;
+    for (int32_t r = nsamp; r < L.max_seqs; ++r) {
+      rfi[r] = r;
+      rln[r] = 1;
+    }
+    ++stat_draft_steps_;
+  }
   counts[10] = npair;            // words of the pair region those rows use
   counts[11] = any_shape ? 1 + nbias : 0;  // a shaped sampling row (logit_bias / min_p pass) + its bias words
   if (nit > L.max_items)  // by construction (psz guard above, max_items sizing) this cannot happen
@@ -1086,6 +1277,8 @@ bool Scheduler::predict(Sequence* s, Planned& e) const {
   if (ng >= s->max_tokens || ntok >= cfg_.max_model_len) return false;
   // penalty counts are sent as known tokens: a penalised row waits for its commit
   if (s->needs_slot()) return false;
+  // a drafting request's step may commit several tokens: nothing to continue from before that
+  if (s->drafting()) return false;
   e.run.clear();
   if (!s->grammar) return true;
   const Grammar& g = *s->grammar;
@@ -1124,6 +1317,14 @@ SeqOutput Scheduler::finish(Sequence* s, int32_t reason, double now) {
   o.lp_records = std::move(s->lp_records);
   s->lp_records.clear();
   if (s->scoring()) --score_live_;
+  if (s->drafting()) {
+    --draft_live_;
+    o.draft_proposed = s->draft_proposed;
+    o.draft_accepted = s->draft_accepted;
+    o.prediction_matched = s->prediction_matched;
+    draft_counts_.push_back({s->id, s->draft_proposed, s->draft_accepted, s->prediction_matched});
+    s->draft_len = 0;  // counted once
+  }
   o.score_from = s->score_from;
   o.score_n = s->score_n;
   o.score_records = std::move(s->score_records);
@@ -1137,8 +1338,50 @@ SeqOutput Scheduler::finish(Sequence* s, int32_t reason, double now) {
   return o;
 }
 
+// One sampled token enters the sequence: the grammar advances, the stops and limits are checked,
+// and the grammar's next forced run is appended (jump-forward). `lp`: the token's record, if the
+// step computed one.
+int32_t Scheduler::apply_token(Sequence* s, int32_t tok, const LogprobRecord* lp) {
+  s->tokens.push_back(tok);
+  ++s->num_generated;
+  ++s->num_sampled;
+  if (s->logprobs >= 0) {
+    if (lp) {
+      s->lp_records.push_back(*lp);
+    } else {  // the step computed no records: keep the alignment with the tokens
+      LogprobRecord r = forced_record(tok, 0);
+      r.lp = NAN;
+      s->lp_records.push_back(r);
+    }
+  }
+  int32_t fin = NOT_FINISHED;
+  if (s->grammar) {
+    s->grammar->advance(tok);
+    if (s->grammar->done()) fin = FINISH_STOP;
+  } else if (!s->ignore_eos) {
+    if (std::find(cfg_.eos_ids.begin(), cfg_.eos_ids.end(), tok) != cfg_.eos_ids.end() ||
+        std::find(s->stop_ids.begin(), s->stop_ids.end(), tok) != s->stop_ids.end())
+      fin = FINISH_STOP;
+  }
+  if (fin == NOT_FINISHED && s->num_generated >= s->max_tokens) fin = FINISH_LENGTH;
+  if (fin == NOT_FINISHED && (int32_t)s->tokens.size() >= cfg_.max_model_len) fin = FINISH_LENGTH;
+  if (fin == NOT_FINISHED && s->grammar) {
+    const int32_t room = std::min(s->max_tokens - s->num_generated,
+                                  cfg_.max_model_len - (int32_t)s->tokens.size());
+    const int32_t k = s->grammar->take_forced_run(s->tokens, room);
+    s->num_generated += k;
+    s->num_forced += k;
+    if (s->logprobs >= 0)
+      for (int32_t j = k; j > 0; --j)
+        s->lp_records.push_back(forced_record(s->tokens[s->tokens.size() - j], s->logprobs));
+    if (s->grammar->done()) fin = FINISH_STOP;
+    else if (s->num_generated >= s->max_tokens) fin = FINISH_LENGTH;
+  }
+  return fin;
+}
+
 std::vector<SeqOutput> Scheduler::commit(const int32_t* sampled, int32_t n, const LogprobRecord* lp,
-                                         const ScoreRecord* sc) {
+                                         const ScoreRecord* sc, const int32_t* accept_len) {
   std::vector<SeqOutput> outs;
   if (plans_.empty()) return outs;
   Plan plan = std::move(plans_.front());
@@ -1179,9 +1422,12 @@ std::vector<SeqOutput> Scheduler::commit(const int32_t* sampled, int32_t n, cons
       }
       continue;
     }
+    int32_t row0 = -1;
     if (p.sample) {
       if (idx >= n) break;
+      row0 = idx;
       tok = sampled[idx++];
+      idx += (int32_t)p.draft.size();  // a draft entry's other rows
     }
     if (p.voided || s->done || s->abort_pending) continue;
     if (!p.sample) {
@@ -1194,40 +1440,42 @@ std::vector<SeqOutput> Scheduler::commit(const int32_t* sampled, int32_t n, cons
     }
     const int32_t before = (int32_t)s->tokens.size();
     if (s->t_first_token < 0) s->t_first_token = now;
-    s->tokens.push_back(tok);
-    ++s->num_generated;
-    ++s->num_sampled;
-    if (s->logprobs >= 0) {
-      if (lp) {
-        s->lp_records.push_back(lp[idx - 1]);
-      } else {  // the step computed no records: keep the alignment with the tokens
-        LogprobRecord r = forced_record(tok, 0);
-        r.lp = NAN;
-        s->lp_records.push_back(r);
-      }
-    }
     int32_t fin = NOT_FINISHED;
-    if (s->grammar) {
-      s->grammar->advance(tok);
-      if (s->grammar->done()) fin = FINISH_STOP;
-    } else if (!s->ignore_eos) {
-      if (std::find(cfg_.eos_ids.begin(), cfg_.eos_ids.end(), tok) != cfg_.eos_ids.end() ||
-          std::find(s->stop_ids.begin(), s->stop_ids.end(), tok) != s->stop_ids.end())
-        fin = FINISH_STOP;
-    }
-    if (fin == NOT_FINISHED && s->num_generated >= s->max_tokens) fin = FINISH_LENGTH;
-    if (fin == NOT_FINISHED && (int32_t)s->tokens.size() >= cfg_.max_model_len) fin = FINISH_LENGTH;
-    if (fin == NOT_FINISHED && s->grammar) {
-      const int32_t room = std::min(s->max_tokens - s->num_generated,
-                                    cfg_.max_model_len - (int32_t)s->tokens.size());
-      const int32_t k = s->grammar->take_forced_run(s->tokens, room);
-      s->num_generated += k;
-      s->num_forced += k;
-      if (s->logprobs >= 0)
-        for (int32_t j = k; j > 0; --j)
-          s->lp_records.push_back(forced_record(s->tokens[s->tokens.size() - j], s->logprobs));
-      if (s->grammar->done()) fin = FINISH_STOP;
-      else if (s->num_generated >= s->max_tokens) fin = FINISH_LENGTH;
+    if (p.draft.empty()) {
+      fin = apply_token(s, tok, lp ? lp + row0 : nullptr);
+      follow_prediction(s, (size_t)before);
+    } else {
+      // a run of 1 + k rows: y_0 .. y_a are committed one by one. The rows behind y_0 were
+      // planned on a copy of the grammar cursor, so the forced run a token's commit appends
+      // (jump-forward) is the run's own next tokens: those are skipped, not appended twice.
+      const int32_t k = (int32_t)p.draft.size();
+      const int32_t* ys = sampled + row0;
+      int32_t a = accept_len ? std::max(0, std::min(accept_len[row0] - 1, k)) : 0;
+      if (row0 + k >= n) a = 0;  // fewer rows than planned: trust the first only
+      for (int32_t j = 0; j < a; ++j)  // the device's count, never past the first host mismatch
+        if (ys[j] != p.draft[j]) a = j;
+      int32_t j = 0;
+      while (j <= a && fin == NOT_FINISHED) {
+        const size_t at = s->tokens.size();
+        fin = apply_token(s, ys[j], nullptr);
+        const int32_t m = (int32_t)(s->tokens.size() - at) - 1;  // forced tokens behind y_j
+        const int32_t use = std::min(m, a - j);
+        if (!std::equal(ys + j + 1, ys + j + 1 + use, s->tokens.begin() + at + 1)) {
+          a = j;  // cannot happen (same automaton, same tokens): keep what the grammar says
+          break;
+        }
+        j += 1 + use;
+      }
+      // KV is valid for the run's inputs up to the last confirmed draft token; everything the
+      // run wrote behind that is dead and is overwritten when those positions are computed
+      // (a stop inside the run: every token committed before it was a confirmed draft token)
+      const int32_t confirmed = std::min(a, (int32_t)s->tokens.size() - before);
+      s->num_computed = std::min(p.end - k + confirmed, (int32_t)s->tokens.size() - 1);
+      s->draft_accepted += confirmed;
+      stat_draft_accepted_ += confirmed;
+      if (confirmed == k) ++stat_draft_full_;
+      const int32_t followed = follow_prediction(s, (size_t)before);
+      s->prediction_matched += p.draft_pred ? followed : confirmed;
     }
     // check the speculative continuation the in-flight step holds for this row
     if (next && s->spec_plan == next->id) {
@@ -1319,6 +1567,19 @@ std::vector<int32_t> Scheduler::take_embed_resets() {
   std::vector<int32_t> r;
   r.swap(embed_resets_);
   return r;
+}
+
+std::vector<Scheduler::DraftCounts> Scheduler::take_draft_counts() {
+  std::vector<DraftCounts> r;
+  r.swap(draft_counts_);
+  return r;
+}
+
+std::vector<int32_t> Scheduler::planned_draft(int64_t id) const {
+  if (!plans_.empty())
+    for (const Planned& p : plans_.back().rows)
+      if (p.s->id == id && !p.s->done) return p.draft;
+  return {};
 }
 
 void Scheduler::reset_prefix_cache() {

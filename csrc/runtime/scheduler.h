@@ -153,9 +153,20 @@ struct StepLayout {
   int32_t n_copies;
   int32_t copy_list;  // [3 * max_seqs]
   int32_t copy_total;
+  // draft steps (predicted outputs / prompt-lookup drafts; csrc/ops/spec_verify.hip), behind
+  // copy_total: written and copied only by steps in which a request owns draft rows, which set
+  // bit 29 of counts[9]. Every sampling row r of such a step carries the run it belongs to:
+  // rows [run_first[r], run_first[r] + run_len[r]) are one request's, a plain row is (r, 1).
+  // copy_total and everything before it keep their values; spec_total is the whole buffer, and a
+  // scheduler whose buffer is not stated to be that long plans no drafts.
+  int32_t run_first;  // [max_seqs]
+  int32_t run_len;    // [max_seqs]
+  int32_t spec_total;
 };
 
 constexpr int32_t COUNTS9_SCORE_BIT = 1 << 30;  // counts[9]: the step has scoring rows
+constexpr int32_t COUNTS9_SPEC_BIT = 1 << 29;   // counts[9]: the step has draft rows (above the repetition words)
+constexpr int32_t MAX_DRAFT_LEN = 8;            // draft tokens of one run (add_request clamps draft_len)
 
 constexpr int32_t LOGIT_BIAS_MAX = 300;  // entries of one request's logit_bias
 
@@ -203,6 +214,10 @@ struct SeqOutput {
   int32_t score_from = -1;  // scoring request: the first scored prompt position (-1: not one)
   int32_t score_n = 0;      // ... and the alternatives it asked for
   std::vector<ScoreRecord> score_records;  // FINISH_SCORE: prompt_len - score_from entries
+  // drafting request: draft tokens proposed; those the sampler confirmed; and the tokens of draft
+  // steps that moved the prediction cursor (confirmed prediction drafts, plus a run's own last
+  // token when it equals the next prediction token) -- all 0 for any other request
+  int32_t draft_proposed = 0, draft_accepted = 0, prediction_matched = 0;
 };
 
 struct Sequence {
@@ -260,6 +275,18 @@ struct Sequence {
   bool scoring() const { return score_from >= 0; }
   // tokens whose KV / logits the request still needs: all of them, or all but a scoring request's last
   int32_t compute_len() const { return (int32_t)tokens.size() - (scoring() ? 1 : 0); }
+  // drafting request (draft_len > 0 and a draft source): when its decode row is planned, up to
+  // draft_len tokens are proposed behind it and verified in the same step (Scheduler::propose).
+  // pred_c: the prediction cursor; pred_synced: prediction[pred_c] is aligned with the next
+  // token to generate (true at the start, kept while committed tokens follow the prediction,
+  // regained by the n-gram resync)
+  std::vector<int32_t> prediction;
+  bool prompt_lookup = false;
+  int32_t draft_len = 0;
+  int32_t pred_c = 0;
+  bool pred_synced = true;
+  int32_t draft_proposed = 0, draft_accepted = 0, prediction_matched = 0;
+  bool drafting() const { return draft_len > 0 && (!prediction.empty() || prompt_lookup); }
   bool ignore_eos = false;
   std::vector<int32_t> stop_ids;
   int64_t arrival = 0;
@@ -306,7 +333,13 @@ class Scheduler {
                    // k in [1, prompt_len - 1]: a scoring request over prompt positions k .. len-1
                    // (`logprobs` = its alternatives, 0..20; nothing is generated; grammar, penalties,
                    // logit_bias, min_p and embed are not allowed); anything else but -1 throws
-                   int32_t score_from = -1);
+                   int32_t score_from = -1,
+                   // drafts (see Sequence): `prediction` token ids the reply is expected to repeat,
+                   // `prompt_lookup` n-gram drafts from the request's own tokens, `draft_len` the
+                   // tokens proposed per step (0 = off, at most MAX_DRAFT_LEN). A request with a
+                   // draft source and draft_len > 0 takes no logprobs, penalties, score_from or embed
+                   // (std::invalid_argument); without a source, or with draft_len 0, nothing changes
+                   std::vector<int32_t> prediction = {}, bool prompt_lookup = false, int32_t draft_len = 0);
   bool abort(int64_t id);
   // Fill `buf` (layout()) for the next step. Returns the number of tokens in the
   // step (0 = nothing to run).
@@ -329,17 +362,38 @@ class Scheduler {
   // request with a repetition penalty gets an error, never a write past its buffer.
   // The same holds one region further for scoring requests: once one has been added, schedule()
   // throws unless buf_words >= layout().score_total.
+  // Drafts are planned only into a buffer stated to hold layout().spec_total words, and never
+  // while a step is in flight (pipelined use): otherwise a drafting request decodes plainly.
   int32_t schedule(int32_t* buf, int32_t buf_words = 0);
   // Consume the sampled tokens of the oldest uncommitted step (one per sampling row).
   // `lp`: the step's log-probability records, one per sampling row (nullptr: the step computed
   // none); rows of requests that did not ask hold nothing meaningful and are not read.
   // `sc`: the step's score records, indexed by row like `sampled` (a scoring row counts as one of
   // the n rows; its sampled token is ignored); nullptr: the step computed none.
+  // `accept_len`: the step's acceptance lengths, indexed by row like `sampled`
+  // (csrc/ops/spec_verify.hip: a + 1 on the first row of a run). A run of 1 + k rows commits its
+  // first a + 1 tokens, each exactly as a one-token commit would (grammar advance, stops,
+  // jump-forward); a stop inside the run drops the rest. nullptr: every run commits one token.
   std::vector<SeqOutput> commit(const int32_t* sampled, int32_t n, const LogprobRecord* lp = nullptr,
-                                const ScoreRecord* sc = nullptr);
+                                const ScoreRecord* sc = nullptr, const int32_t* accept_len = nullptr);
   int32_t inflight_steps() const { return (int32_t)plans_.size(); }
   int64_t spec_rows() const { return stat_spec_rows_; }
   int64_t spec_voided() const { return stat_spec_voided_; }
+  // drafts: tokens proposed, tokens the sampler confirmed, steps with draft rows, runs whose
+  // whole draft was confirmed
+  int64_t spec_draft_tokens() const { return stat_draft_tokens_; }
+  int64_t spec_accepted_tokens() const { return stat_draft_accepted_; }
+  int64_t spec_draft_steps() const { return stat_draft_steps_; }
+  int64_t spec_runs_full() const { return stat_draft_full_; }
+  // (id, proposed, accepted, prediction_matched) of the drafting requests finished since the
+  // last call (the SeqOutput fields, for callers that read outputs as tuples)
+  struct DraftCounts {
+    int64_t id;
+    int32_t proposed, accepted, matched;
+  };
+  std::vector<DraftCounts> take_draft_counts();
+  // the draft of the request's entry in the step scheduled last (empty: none), for diagnostics
+  std::vector<int32_t> planned_draft(int64_t id) const;
   // Finished-by-abort outputs are returned here as well.
   std::vector<SeqOutput> drain_aborted();
 
@@ -404,7 +458,17 @@ class Scheduler {
     int32_t src_idx = -1;         // spec: sampling row of the pending token in the previous plan
     std::vector<int32_t> run;     // spec: predicted forced tokens after the pending token
     Grammar::Cursor cur;          // spec: predicted automaton state before this entry's sample
+    // draft entry: the last `draft.size()` of the n tokens are proposed, not yet real; the entry
+    // owns 1 + draft.size() sampling rows, row j with the grammar's (class, forced) in row_gram[j]
+    std::vector<int32_t> draft;
+    std::vector<std::pair<int32_t, int32_t>> row_gram;
+    bool draft_pred = false;      // the draft comes from the prediction (at pred_c), not from lookup
   };
+  // up to k draft tokens for the decode row of `s` (empty: none); may move the prediction cursor
+  std::vector<int32_t> propose(Sequence* s, int32_t k, bool* from_prediction) const;
+  // one committed token: what a one-token commit applies. Returns the finish reason.
+  int32_t apply_token(Sequence* s, int32_t tok, const LogprobRecord* lp);
+  int32_t follow_prediction(Sequence* s, size_t from);  // -> tokens that were the prediction's next
   struct Plan {
     int64_t id;
     std::vector<Planned> rows;
@@ -423,6 +487,10 @@ class Scheduler {
   bool rep_requested_ = false;         // a request with a repetition penalty was added: see schedule()
   bool score_requested_ = false;       // a scoring request was added: see schedule() (the buffer's size)
   int32_t score_live_ = 0;             // scoring requests not yet finished: the row budget applies
+  int32_t draft_live_ = 0;             // drafting requests not yet finished: the row budget applies
+  bool drafts_ok_ = false;             // the buffer of the schedule() call in progress holds the run regions
+  int64_t stat_draft_tokens_ = 0, stat_draft_accepted_ = 0, stat_draft_steps_ = 0, stat_draft_full_ = 0;
+  std::vector<DraftCounts> draft_counts_;
   int64_t arrival_counter_ = 0;
   int64_t stat_prompt_tokens_ = 0, stat_cached_tokens_ = 0, stat_preemptions_ = 0, stat_steps_ = 0;
   int64_t stat_aligned_steps_ = 0;

@@ -88,6 +88,9 @@ class LLMConfig(BaseModel):
     # multiplicative repetition penalty over the prompt and the reply so far (the HF / vLLM rule),
     # the request default (1 = off)
     repetition_penalty: float = Field(default=1.0, gt=0.0, le=2.0)
+    # prompt-lookup drafts, the request default (off): decode steps propose the continuation of the
+    # last tokens' latest earlier occurrence in the prompt or the reply and verify it at once
+    prompt_lookup: bool = False
     max_tokens: int = Field(default=2000, gt=0)
     function_calling_model: Optional[str] = None
     system_template: Optional[str] = None

@@ -159,6 +159,12 @@ class EngineConfig:
     # requests with a non-zero penalty run at once, further ones wait for a slot. The state
     # (slots x vocabulary int32 counts, 33 MB at 64 x 128,256) is allocated on the first such request.
     penalty_slots: int = 64
+    # drafts (submit(prediction=, prompt_lookup=)): tokens proposed behind a drafting request's
+    # decode row and verified in the same step (runtime/scheduler.h, csrc/ops/spec_verify.hip).
+    # 3: with the 8B model's 4 query heads per KV head the 1 + 3-token run is exactly one kv-split
+    # attention item; longer runs become narrow prefill items. max_draft_len bounds submit(draft_len=).
+    draft_len: int = 3
+    max_draft_len: int = 8
 
 
 # TP step header: [op, T, ns, nsamp, bucket, masks_changed, n_copy, truncate, embed]
@@ -190,6 +196,11 @@ class GenerationOutput:
     # the <= n most likely tokens); natural log of softmax(logits) over the whole vocabulary at
     # temperature 1. finish_reason is "score", token_ids is empty, cumulative_logprob their sum
     prompt_logprobs: Optional[List[Tuple[float, int, List[Tuple[int, float]]]]] = field(default=None, repr=False)
+    # submit(prediction= / prompt_lookup=): tokens of the reply that draft steps took from the
+    # prediction or the lookup (confirmed draft tokens, plus a step's own last token when it is the
+    # prediction's next one), and proposed draft tokens the sampler did not confirm; 0 otherwise
+    accepted_prediction_tokens: int = 0
+    rejected_prediction_tokens: int = 0
 
     @property
     def text(self) -> str:
@@ -232,6 +243,9 @@ class _Request:
     repetition_penalty: float = 1.0      # 1 off; else in (0, 2]
     inv_repetition_penalty: float = 1.0  # float32(1 / r), computed once here for host and device
     score_from: int = -1                 # -1 off; k: a scoring request over prompt positions k .. len-1
+    prediction: tuple = ()               # token ids the reply is expected to repeat (draft source)
+    prompt_lookup: bool = False          # n-gram drafts from the request's own tokens
+    draft_len: int = 0                   # draft tokens per step; 0 = not a drafting request
 
 
 class LLMEngine:
@@ -342,11 +356,11 @@ class LLMEngine:
         # one being scheduled); the device copy is stream-ordered behind the previous step
         self._async = bool(cfg.async_steps) and self.tp.size == 1
         nbuf = 2 if self._async else 1
-        self._host_metas = [torch.zeros(L["copy_total"], dtype=torch.int32, pin_memory=pin) for _ in range(nbuf)]
+        self._host_metas = [torch.zeros(L["spec_total"], dtype=torch.int32, pin_memory=pin) for _ in range(nbuf)]
         self._host_meta = self._host_metas[0]
         self._host_ptr = self._host_meta.data_ptr()
         self._host_np = self._host_meta.numpy()
-        self._dev_meta = torch.zeros(L["copy_total"], dtype=torch.int32, device=self.device) \
+        self._dev_meta = torch.zeros(L["spec_total"], dtype=torch.int32, device=self.device) \
             if (self.on_gpu or self._async) else self._host_meta
         # attention tickets: one per (sequence, KV head) for split decode rows, then -- only with
         # prefill_split_keys on -- one per (partial slot, KV head) for split prefill items
@@ -419,6 +433,13 @@ class LLMEngine:
         self._sc_ws = ops.score_tokens_workspace(S, self.model.v_local, self.device) \
             if (self.on_gpu and self.tp.size == 1) else None
         self._score_bit = int(self._rt.Scheduler.COUNTS9_SCORE_BIT)
+        # draft steps (submit(prediction= / prompt_lookup=)): ops.spec_verify takes the place of the
+        # sampler's final merge in the step graph's draft variant and writes, beside the sampled
+        # tokens, the acceptance length of every run; both are copied to the host together
+        self._spec_bit = int(self._rt.Scheduler.COUNTS9_SPEC_BIT)
+        self._accept_dev = torch.zeros(S4, dtype=torch.int32, device=self.device)
+        self._accept_hosts = [torch.zeros(S, dtype=torch.int32, pin_memory=pin) for _ in range(nbuf)]
+        self._draft_counts: Dict[int, tuple] = {}  # request id -> (proposed, accepted, prediction matched)
         # presence / frequency penalties (submit(presence_penalty=, frequency_penalty=)): per-slot
         # token counts on the device, allocated on the first penalised request; ops.apply_penalties
         # rewrites the logits behind the LM head in the step graph's penalty variant
@@ -435,7 +456,8 @@ class LLMEngine:
         # with a penalised row the 5-tuple key (bucket, trunc, embed, lp, True), a step with a
         # logit_bias / min_p row the 6-tuple key (bucket, trunc, embed, lp, pen, True), a step
         # with a repetition-penalty row the 7-tuple key (bucket, trunc, embed, lp, pen, shape, True),
-        # a step with scoring rows the 8-tuple key (bucket, trunc, embed, lp, pen, shape, rep, True).
+        # a step with scoring rows the 8-tuple key (bucket, trunc, embed, lp, pen, shape, rep, True),
+        # a step with draft rows the 9-tuple key (bucket, trunc, embed, lp, pen, shape, rep, score, True).
         self._graphs: Dict[tuple, "torch.cuda.CUDAGraph"] = {}
         self._tau = torch.empty(S, dtype=torch.float32, device=self.device)
         self._graph_pool = None
@@ -547,6 +569,8 @@ class LLMEngine:
         self._score_target = sl("score_target", ms)
         self._n_copies = sl("n_copies", 1)
         self._copy_list = sl("copy_list", 3 * ms)
+        self._run_first = sl("run_first", ms)
+        self._run_len = sl("run_len", ms)
 
     def _sync_masks(self) -> bool:
         reg = self.grammar.reg
@@ -581,7 +605,7 @@ class LLMEngine:
 
     def _forward_and_sample(self, bucket: int, s_b: int, ns: int, trunc: bool = False, embed: bool = False,
                             lp: bool = False, pen: bool = False, shape: bool = False, rep: bool = False,
-                            score: bool = False):
+                            score: bool = False, spec: bool = False):
         meta = self._meta_for(bucket, s_b, ns)
         if self._partial:
             # partial-block prefix hits: the cached heads go into the new blocks before any layer
@@ -626,7 +650,16 @@ class LLMEngine:
             tau = ops.minp_threshold(logits, self._temp[:s_b], self._minp[:s_b], self._ln_minp[:s_b],
                                      self._forced[:s_b], self._mask_cls[:s_b], self._class_masks,
                                      tau=tau, out=self._tau[:s_b])
-        if self.tp.size == 1:
+        if spec:
+            # a draft step (TP = 1): the sampler's chunk pass, then one launch that merges the
+            # partials like the sampler's final kernel and checks every run's draft against them
+            pk, pi = ops.sample_partials(logits, self._temp[:s_b], self._mask_cls[:s_b], self._class_masks,
+                                         self._seeds[:s_b], self._offsets[:s_b], workspace=self._sample_ws,
+                                         tau=tau)
+            ops.spec_verify(pk, pi, self._forced[:s_b], self.meta.input_ids, self.meta.logit_rows[:s_b],
+                            self._run_first[:s_b], self._run_len[:s_b], out_tokens=self._sampled_dev[:s_b],
+                            accept_len=self._accept_dev[:s_b])
+        elif self.tp.size == 1:
             ops.sample(logits, self._temp[:s_b], self._mask_cls[:s_b], self._class_masks,
                        self._seeds[:s_b], self._offsets[:s_b], self._forced[:s_b],
                        out=self._sampled_dev[:s_b], workspace=self._sample_ws, tau=tau)
@@ -656,7 +689,9 @@ class LLMEngine:
 
     @staticmethod
     def _graph_key(bucket: int, trunc: bool, embed: bool, lp: bool = False, pen: bool = False,
-                   shape: bool = False, rep: bool = False, score: bool = False) -> tuple:
+                   shape: bool = False, rep: bool = False, score: bool = False, spec: bool = False) -> tuple:
+        if spec:
+            return (bucket, trunc, embed, lp, pen, shape, rep, score, True)
         if score:
             return (bucket, trunc, embed, lp, pen, shape, rep, True)
         if rep:
@@ -668,8 +703,9 @@ class LLMEngine:
         return (bucket, trunc, embed, True) if lp else (bucket, trunc, embed)
 
     def _run(self, bucket: int, ns: int, trunc: bool, n_copy: int, embed: bool = False, lp: bool = False,
-             pen: bool = False, shape: bool = False, rep: bool = False, score: bool = False):
-        """Replay the (bucket, trunc, embed[, logprobs[, penalties[, shaping[, repetition[, scoring]]]]]) graph
+             pen: bool = False, shape: bool = False, rep: bool = False, score: bool = False,
+             spec: bool = False):
+        """Replay the (bucket, trunc, embed[, logprobs[, penalties[, shaping[, repetition[, scoring[, drafts]]]]]]) graph
         — capturing it first if needed — or run eagerly."""
         if pen:
             self._ensure_pen_state()
@@ -677,19 +713,19 @@ class LLMEngine:
             self._ensure_rep_state()
         if not self.use_graphs:
             self._forward_and_sample(bucket, self._seq_bucket(bucket), ns, trunc, embed, lp, pen, shape, rep,
-                                     score)
+                                     score, spec)
             return
-        key = self._graph_key(bucket, trunc, embed, lp, pen, shape, rep, score)
+        key = self._graph_key(bucket, trunc, embed, lp, pen, shape, rep, score, spec)
         g = self._graphs.get(key)
         if g is None:
-            # the regions of shaped / repetition / scoring rows and the copy list lie behind the
-            # copied prefix: keep the whole buffer
-            n_copy = self.L["copy_total"]
+            # the regions of shaped / repetition / scoring rows, the copy list and the runs lie
+            # behind the copied prefix: keep the whole buffer
+            n_copy = self.L["spec_total"]
             saved = self._dev_meta[:n_copy].clone()
             pool = self._embed_pool.clone()
             samp = self._sampled_dev.clone()  # the previous step's tokens (pipelined mode)
             self.capture_graphs([bucket], trunc=trunc, embed=embed, lp=lp, pen=pen,
-                                shape=shape, rep=rep, score=score)  # clobbers the device metadata
+                                shape=shape, rep=rep, score=score, spec=spec)  # clobbers the device metadata
             self.stats["graph_captures"] += 1  # a first-use capture inside serving (tens of ms)
             self._dev_meta[:n_copy].copy_(saved)
             self._embed_pool.copy_(pool)
@@ -713,6 +749,11 @@ class LLMEngine:
         a, b = self.L["score_target"], self.L["score_target"] + self.L["max_seqs"]
         self._dev_meta[a:b].copy_(hm[a:b], non_blocking=self.on_gpu)
 
+    def _copy_runs(self, hm: torch.Tensor):
+        """Host -> device copy of the run regions of a draft step (run_first and run_len, adjacent)."""
+        a, b = self.L["run_first"], self.L["run_len"] + self.L["max_seqs"]
+        self._dev_meta[a:b].copy_(hm[a:b], non_blocking=self.on_gpu)
+
     def _copy_copies(self, hm: torch.Tensor, n: int):
         """Host -> device copy of the `n` partial-block copy triples of a step that has some (the
         count itself lies in the header every step copies)."""
@@ -731,13 +772,15 @@ class LLMEngine:
     def _dummy_meta(self):
         """A metadata state under which a forward touches no KV and no attention item."""
         L = self.L
-        d = torch.zeros(L["copy_total"], dtype=torch.int32)  # n_copies = 0: the copy kernel touches nothing
+        d = torch.zeros(L["spec_total"], dtype=torch.int32)  # n_copies = 0: the copy kernel touches nothing
         d[L["slots"]:L["slots"] + L["max_tokens"]] = -1
         d[L["embed_rows"]:L["embed_rows"] + L["max_tokens"]] = L["max_seqs"]
         d[L["pen_slot"]:L["pen_slot"] + L["max_seqs"]] = -1  # the penalty pass touches nothing
         # bias_n = 0 and min_p = 0 (the zeros above): the logit_bias / min_p passes touch nothing
         d[L["rep_slot"]:L["rep_slot"] + L["max_seqs"]] = -1  # the repetition pass touches nothing
         d[L["score_target"]:L["score_target"] + L["max_seqs"]] = -1  # the scoring pass touches nothing
+        d[L["run_first"]:L["run_first"] + L["max_seqs"]] = torch.arange(L["max_seqs"], dtype=torch.int32)
+        d[L["run_len"]:L["run_len"] + L["max_seqs"]] = 1  # every row a run of its own
         self._dev_meta.copy_(d.to(self.device))
 
     def capture_embed_graphs(self):
@@ -749,11 +792,11 @@ class LLMEngine:
 
     def capture_graphs(self, buckets: Optional[Sequence[int]] = None, trunc: bool = False, embed: bool = False,
                        lp: bool = False, pen: bool = False, shape: bool = False, rep: bool = False,
-                       score: bool = False):
+                       score: bool = False, spec: bool = False):
         """Capture one hipGraph per token bucket (shared memory pool); the top-k/top-p,
         embedding-pooling, log-probability, penalty, logit_bias / min_p (`shape`), repetition
-        penalty (`rep`) and prompt-scoring (`score`) variants are captured on first use, or up front
-        by a call with the flag set."""
+        penalty (`rep`), prompt-scoring (`score`) and draft (`spec`) variants are captured on
+        first use, or up front by a call with the flag set."""
         if not self.use_graphs:
             return
         if pen:
@@ -765,7 +808,7 @@ class LLMEngine:
             self._graph_pool = torch.cuda.graph_pool_handle()
         t0 = time.time()
         for b in sorted(buckets or self.buckets, reverse=True):
-            key = self._graph_key(b, trunc, embed, lp, pen, shape, rep, score)
+            key = self._graph_key(b, trunc, embed, lp, pen, shape, rep, score, spec)
             if key in self._graphs:
                 continue
             s_b = self._seq_bucket(b)
@@ -773,11 +816,11 @@ class LLMEngine:
             st.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(st):
                 for _ in range(2):
-                    self._forward_and_sample(b, s_b, 0, trunc, embed, lp, pen, shape, rep, score)
+                    self._forward_and_sample(b, s_b, 0, trunc, embed, lp, pen, shape, rep, score, spec)
             torch.cuda.current_stream().wait_stream(st)
             g = torch.cuda.CUDAGraph(keep_graph=True) if self.cfg.keep_graphs else torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, pool=self._graph_pool):
-                self._forward_and_sample(b, s_b, 0, trunc, embed, lp, pen, shape, rep, score)
+                self._forward_and_sample(b, s_b, 0, trunc, embed, lp, pen, shape, rep, score, spec)
             if self.cfg.keep_graphs:
                 g.instantiate()
             self._graphs[key] = g
@@ -835,7 +878,9 @@ class LLMEngine:
                request_id: Optional[int] = None, top_k: int = 0, top_p: float = 1.0,
                embed: Union[bool, str] = False, logprobs: int = -1, presence_penalty: float = 0.0,
                frequency_penalty: float = 0.0, logit_bias: Optional[Mapping[int, float]] = None,
-               min_p: float = 0.0, repetition_penalty: float = 1.0, score_from: Optional[int] = None) -> int:
+               min_p: float = 0.0, repetition_penalty: float = 1.0, score_from: Optional[int] = None,
+               prediction: Sequence[int] = (), prompt_lookup: bool = False,
+               draft_len: Optional[int] = None) -> int:
         """Thread-safe; `callback` runs on the engine thread when the request finishes.
 
         top_k > 0 / top_p < 1 truncate the (grammar-masked) distribution before
@@ -888,9 +933,29 @@ class LLMEngine:
         cumulative_logprob the sum. Positions before k - 1 may come from the prefix cache and the
         request's blocks are cached like any other's, so K candidates over one context pay for the
         context once. temperature, top_k, top_p, seed and max_tokens are ignored; embed, a grammar,
-        any penalty, logit_bias, min_p and repetition_penalty are refused, as is a TP > 1 engine."""
+        any penalty, logit_bias, min_p and repetition_penalty are refused, as is a TP > 1 engine.
+
+        prediction (token ids the reply is expected to repeat: OpenAI's Predicted Outputs) and
+        prompt_lookup (n-gram drafts from the request's own prompt and reply) make a drafting
+        request: when its decode row is planned, up to draft_len (None: EngineConfig.draft_len;
+        0 = off; at most EngineConfig.max_draft_len) tokens are proposed behind it and run in the
+        same step, one sampling row each, and the device keeps the tokens up to the first row
+        whose sample differs from its draft token (csrc/ops/spec_verify.hip). The sampler's noise
+        is keyed on (seed, position, vocab index), so every emitted token is the token a plain
+        step samples at that position from the same logits: no rejection sampling, greedy and
+        sampled alike. The prediction is followed by a cursor that resyncs on the last 4 / 3 / 2
+        tokens after a mismatch; prompt lookup runs when the prediction proposes nothing
+        (runtime/scheduler.cpp propose). Works with grammars, temperature / top_k / top_p / seed,
+        logit_bias and min_p; the output carries accepted_prediction_tokens /
+        rejected_prediction_tokens. A draft never preempts a request and never takes a sampling
+        row from a plain decode row. draft_len without a prediction or prompt_lookup changes
+        nothing. Refused: prediction ids outside the vocabulary, draft_len outside
+        [0, max_draft_len], logprobs, any penalty, score_from, embed, a TP > 1 engine, async_steps."""
         if self._err is not None:
             raise RuntimeError(f"engine failed: {self._err!r}")
+        pred, n_draft = self._check_drafts(prediction, prompt_lookup, draft_len)
+        if n_draft and score_from is not None:
+            raise ValueError("prediction / prompt_lookup are not available on a scoring request")
         if score_from is not None:
             return self._submit_score(prompt_ids, callback, score_from, logprobs, request_id,
                                       dict(embed=embed, grammar=grammar, presence_penalty=presence_penalty,
@@ -935,6 +1000,15 @@ class LLMEngine:
                 raise ValueError("repetition_penalty is not supported on an async_steps engine")
             if self._pen_slots < 1:
                 raise ValueError("repetition_penalty needs EngineConfig.penalty_slots >= 1")
+        if n_draft:
+            if embed:
+                raise ValueError("prediction / prompt_lookup are not available on embedding requests")
+            if logprobs >= 0:
+                raise ValueError("prediction / prompt_lookup are not supported together with logprobs")
+            if pens[0] != 0.0 or pens[1] != 0.0 or rep_r != 1.0:
+                raise ValueError("prediction / prompt_lookup are not supported together with presence_penalty, "
+                                 "frequency_penalty or repetition_penalty (their device state is kept per "
+                                 "committed token)")
         rid = request_id if request_id is not None else self.new_request_id()
         if seed is None:
             seed = (self.cfg.seed * 0x9E3779B1 + rid * 0x85EBCA77) & 0x7FFFFFFFFFFFFFFF
@@ -942,10 +1016,32 @@ class LLMEngine:
                        bool(ignore_eos), list(stop_ids), grammar, callback, self._rt.now(),
                        int(top_k or 0), float(1.0 if top_p is None else top_p), bool(embed), embed == "last",
                        logprobs, pens[0], pens[1], bias, min_p, ref_ln_min_p(min_p), rep_r,
-                       ref_inv_repetition_penalty(rep_r))
+                       ref_inv_repetition_penalty(rep_r), prediction=pred if n_draft else (),
+                       prompt_lookup=bool(prompt_lookup) and n_draft > 0, draft_len=n_draft)
         self._inbox.put(req)
         self._wake.set()
         return rid
+
+    def _check_drafts(self, prediction, prompt_lookup, draft_len) -> Tuple[tuple, int]:
+        """Validate submit()'s draft arguments: (prediction ids, draft tokens per step -- 0 when the
+        request has no draft source or drafts are off); ValueError for anything outside the rules."""
+        K = self.cfg.draft_len if draft_len is None else draft_len
+        if isinstance(K, bool) or not isinstance(K, Integral) or not 0 <= K <= self.cfg.max_draft_len:
+            raise ValueError(f"draft_len must be an integer in [0, {self.cfg.max_draft_len}], not {K!r}")
+        if K > self._rt.Scheduler.MAX_DRAFT_LEN:
+            raise ValueError(f"draft_len {K} exceeds the scheduler's limit {self._rt.Scheduler.MAX_DRAFT_LEN}")
+        pred = () if prediction is None else tuple(prediction)
+        V = self.model_cfg.vocab_size
+        for t in pred:
+            if isinstance(t, bool) or not isinstance(t, Integral) or not 0 <= t < V:
+                raise ValueError(f"prediction token id {t!r} is not an integer in [0, {V})")
+        if not pred and not prompt_lookup:
+            return (), 0
+        if self.tp.size > 1:
+            raise ValueError("prediction / prompt_lookup are not supported on a tensor-parallel (TP > 1) engine")
+        if self.cfg.async_steps:
+            raise ValueError("prediction / prompt_lookup are not supported on an async_steps engine")
+        return tuple(int(t) for t in pred), int(K)
 
     def _submit_score(self, prompt_ids, callback, score_from, logprobs, request_id, others) -> int:
         """submit(score_from=k): validate and queue a scoring request."""
@@ -1247,7 +1343,8 @@ class LLMEngine:
                                    req.ignore_eos, req.stop_ids, req.grammar, req.top_k, req.top_p, req.embed,
                                    req.embed_last, req.logprobs, req.presence_penalty, req.frequency_penalty,
                                    list(req.logit_bias), req.min_p, req.ln_min_p, req.repetition_penalty,
-                                   req.inv_repetition_penalty, req.score_from)
+                                   req.inv_repetition_penalty, req.score_from, list(req.prediction),
+                                   req.prompt_lookup, req.draft_len)
             self.stats["requests"] += 1
         while True:
             try:
@@ -1280,6 +1377,12 @@ class LLMEngine:
                                lps, None if lps is None else float(sum(e[0] for e in lps)))
         if req.score_from >= 0:  # a scoring request's records are per prompt position: (logprob, rank, top)
             out.logprobs, out.prompt_logprobs = None, lps
+        if req.draft_len > 0:
+            for did, proposed, accepted, matched in self.sched.take_draft_counts():
+                self._draft_counts[did] = (proposed, accepted, matched)
+            proposed, accepted, matched = self._draft_counts.pop(rid, (0, 0, 0))
+            out.accepted_prediction_tokens = matched
+            out.rejected_prediction_tokens = proposed - accepted
         # per-request timings: TTFT = arrival -> first token, TPOT = later tokens' mean gap
         # (generation only: a scoring request has no first token and no token gaps)
         if t_first > 0 and req.score_from < 0:
@@ -1312,7 +1415,8 @@ class LLMEngine:
         ns, nsamp, trunc, embed, lp = int(c[1]), int(c[2]), int(c[6]) > 0, int(c[7]) > 0, int(c[8]) > 0
         pen = (int(c[9]) & 1) > 0
         score = (int(c[9]) & self._score_bit) > 0  # the step has scoring rows
-        rep = (int(c[9]) & (self._score_bit - 1)) >> 1  # 0, or 1 + 2 * the token words of the step's repetition-penalty rows
+        spec = (int(c[9]) & self._spec_bit) > 0  # the step has draft rows
+        rep = (int(c[9]) & (self._spec_bit - 1)) >> 1  # 0, or 1 + 2 * the token words of the step's repetition-penalty rows
         shape = int(c[11])  # 0, or 1 + the bias words of the step's logit_bias / min_p rows
         bucket = next(b for b in self.buckets if b >= T)
         s_b = self._seq_bucket(bucket)
@@ -1331,6 +1435,8 @@ class LLMEngine:
                 self._copy_repetition(self._host_meta, rep >> 1)
             if score:
                 self._copy_scoring(self._host_meta)
+            if spec:
+                self._copy_runs(self._host_meta)
             ncp = int(self._host_np[L["n_copies"]])
             if ncp:
                 self._copy_copies(self._host_meta, ncp)
@@ -1340,11 +1446,13 @@ class LLMEngine:
                 self.tp.broadcast(self._class_masks)
             self.tp.broadcast(self._dev_meta[:n_copy])
         with torch.inference_mode(), trace_range("engine.forward"):
-            self._run(bucket, ns, trunc, n_copy, embed, lp, pen, shape > 0, rep > 0, score)
+            self._run(bucket, ns, trunc, n_copy, embed, lp, pen, shape > 0, rep > 0, score, spec)
         if self._step_listeners:
             self._notify_launch(T)
         if nsamp:
             self._sampled_host[:nsamp].copy_(self._sampled_dev[:nsamp], non_blocking=self.on_gpu)
+        if spec:
+            self._accept_hosts[0][:nsamp].copy_(self._accept_dev[:nsamp], non_blocking=self.on_gpu)
         if lp:
             self._lp_hosts[0][:nsamp].copy_(self._lp_rec[:nsamp], non_blocking=self.on_gpu)
         if score:
@@ -1362,7 +1470,8 @@ class LLMEngine:
         with trace_range("engine.commit"):
             outs = self.sched.commit(self._sampled_host.data_ptr(), nsamp,
                                      self._lp_hosts[0].data_ptr() if lp else 0,
-                                     self._sc_hosts[0].data_ptr() if score else 0)
+                                     self._sc_hosts[0].data_ptr() if score else 0,
+                                     self._accept_hosts[0].data_ptr() if spec else 0)
         if embed:
             self._read_embeddings(outs)
         st = self.stats
@@ -1568,6 +1677,8 @@ class LLMEngine:
             "prefix_defers": s.prefix_defers,
             "partial_hit_tokens": s.partial_hit_tokens, "same_step_shares": s.same_step_shares,
             "spec_rows": s.spec_rows, "spec_voided": s.spec_voided,
+            "spec_draft_tokens": s.spec_draft_tokens, "spec_accepted_tokens": s.spec_accepted_tokens,
+            "spec_draft_steps": s.spec_draft_steps, "spec_runs_full": s.spec_runs_full,
             "kv_cache_gb": self.kv.k.numel() * 2 * 2 / 2**30,
             "weights_gb": self.model.weight_bytes() / 2**30,
         })

@@ -48,6 +48,7 @@ class OpenAICompatLLM(BaseLLM):
         self.schema_mode = schema_mode
         # score() / choose() go to POST /v1/score, which only a pilottai_amd server has
         self.supports_scoring = schema_mode == "pilottai"
+        self.supports_prediction = True  # `prediction` is OpenAI's field; a server may ignore it
         self._client = None
 
     def _http(self):
@@ -85,6 +86,13 @@ class OpenAICompatLLM(BaseLLM):
         rp = rf.get("repetition_penalty", self.repetition_penalty)
         if rp is not None and float(rp) != 1.0:
             body["repetition_penalty"] = float(rp)
+        # OpenAI's Predicted Outputs; prompt_lookup is a pilottai_amd server's extension
+        if rf.get("prediction"):
+            if not isinstance(rf["prediction"], str):
+                raise ValueError("response_format['prediction'] must be a string")
+            body["prediction"] = {"type": "content", "content": rf["prediction"]}
+        if self.schema_mode == "pilottai" and rf.get("prompt_lookup", self.prompt_lookup):
+            body["prompt_lookup"] = True
         if tools:
             body["tools"] = self._format_tools(tools)
         elif rf.get("schema") is not None:
@@ -108,7 +116,10 @@ class OpenAICompatLLM(BaseLLM):
         return {"content": msg.get("content") or "", "role": msg.get("role", "assistant"),
                 "tool_calls": msg.get("tool_calls"), "model": data.get("model", self.model_name),
                 "logprobs": (ch.get("logprobs") or {}).get("content"),
-                "usage": {"prompt_tokens": pt, "completion_tokens": ct, "total_tokens": pt + ct}}
+                "usage": {"prompt_tokens": pt, "completion_tokens": ct, "total_tokens": pt + ct,
+                          "completion_tokens_details": {
+                              k: int((usage.get("completion_tokens_details") or {}).get(k, 0))
+                              for k in ("accepted_prediction_tokens", "rejected_prediction_tokens")}}}
 
     async def score(self, messages_or_text, candidates, top: int = 0) -> List[Dict[str, Any]]:
         """POST /v1/score of a pilottai_amd server (schema_mode "pilottai"); other OpenAI-compatible

@@ -116,6 +116,9 @@ class BaseLLM:
     supports_logit_shaping = False
     supports_repetition_penalty = False  # response_format["repetition_penalty"] is honoured
     supports_scoring = False  # score() / choose(): log-probabilities of given candidate texts
+    # response_format["prediction"] (text the reply is expected to repeat) / ["prompt_lookup"] are
+    # honoured and r["usage"]["completion_tokens_details"] returned
+    supports_prediction = False
 
     async def score(self, messages_or_text: Union[str, Sequence[Dict[str, str]]], candidates: Sequence[str],
                     top: int = 0) -> List[Dict[str, Any]]:
@@ -150,6 +153,8 @@ class BaseLLM:
         # request default of the multiplicative repetition penalty (1 = off)
         rp = _cfg_get(config, "repetition_penalty", 1.0)
         self.repetition_penalty = 1.0 if rp is None else float(rp)
+        # request default of prompt-lookup drafts (off); a prediction has no config default
+        self.prompt_lookup = bool(_cfg_get(config, "prompt_lookup", False))
         self.max_tokens = int(_cfg_get(config, "max_tokens", 2000))
         self.retry_attempts = max(1, int(_cfg_get(config, "retry_attempts", 3)))
         self.retry_delay = float(_cfg_get(config, "retry_delay", 1.0))
@@ -226,6 +231,7 @@ class LocalLLM(BaseLLM):
     supports_logit_shaping = True
     supports_repetition_penalty = True
     supports_scoring = True
+    supports_prediction = True
     prefix_cache_layout = True  # agents put the shared task text first (core/agent.py)
 
     def __init__(self, config: Any = None, engine=None):
@@ -323,6 +329,15 @@ class LocalLLM(BaseLLM):
 
         rf = response_format or {}
         temp = float(rf.get("temperature", self.temperature))
+        # a prediction is text: tokenised on its own, without special tokens (the engine resyncs its
+        # cursor on the reply's tokens, so the boundary to the chat template plays no part)
+        pred = rf.get("prediction")
+        if pred is not None and not isinstance(pred, str):
+            raise ValueError("response_format['prediction'] must be a string")
+        drafts = dict(prediction=self.tok.encode(pred) if pred else (),
+                      prompt_lookup=bool(rf.get("prompt_lookup", self.prompt_lookup)))
+        if rf.get("draft_len") is not None:
+            drafts["draft_len"] = rf["draft_len"]
         rid = self.engine.submit(ids, done, temperature=temp, max_tokens=int(rf.get("max_tokens", self.max_tokens)),
                                  grammar=grammar,
                                  seed=rf.get("seed"), top_k=int(rf.get("top_k", self.top_k)),
@@ -331,7 +346,8 @@ class LocalLLM(BaseLLM):
                                  presence_penalty=rf.get("presence_penalty", self.presence_penalty),
                                  frequency_penalty=rf.get("frequency_penalty", self.frequency_penalty),
                                  logit_bias=rf.get("logit_bias"), min_p=rf.get("min_p", self.min_p),
-                                 repetition_penalty=rf.get("repetition_penalty", self.repetition_penalty))
+                                 repetition_penalty=rf.get("repetition_penalty", self.repetition_penalty),
+                                 **drafts)
         try:
             out = await fut
         except asyncio.CancelledError:
@@ -358,7 +374,10 @@ class LocalLLM(BaseLLM):
             "logprobs": None if out.logprobs is None else logprob_entries(self.tok, out.token_ids, out.logprobs),
             "model": self.engine.model_cfg.name,
             "usage": {"prompt_tokens": out.prompt_tokens, "completion_tokens": out.completion_tokens,
-                      "total_tokens": out.prompt_tokens + out.completion_tokens},
+                      "total_tokens": out.prompt_tokens + out.completion_tokens,
+                      "completion_tokens_details": {
+                          "accepted_prediction_tokens": out.accepted_prediction_tokens,
+                          "rejected_prediction_tokens": out.rejected_prediction_tokens}},
             "timing": {"ttft": out.ttft, "latency": out.latency,
                        "cached_prompt_tokens": out.cached_prompt_tokens,
                        "sampled_tokens": out.sampled_tokens},

@@ -214,6 +214,52 @@ def sample(logits, temperature, mask_class, class_masks, seeds, offsets, forced=
     return toks
 
 
+SPEC_VERIFY_LAUNCHES = 1  # kernels spec_verify() launches on the GPU (it replaces the sampler's final merge)
+NO_TOKEN = 0x7FFFFFFF     # id of a sampler partial with no allowed token
+
+
+def sample_partials(logits, temperature, mask_class, class_masks, seeds, offsets, workspace: torch.Tensor,
+                    tau: Optional[torch.Tensor] = None):
+    """The sampler's chunk pass alone (csrc/ops/sampling.hip): returns (part_k fp32, part_i int32)
+    [rows, nchunk], views of `workspace`, for spec_verify(). On the CPU: one partial per row from
+    the reference sampler."""
+    rows, V = logits.shape
+    if _on_gpu(logits):
+        C = require_native()
+        C.sample_partials(workspace, logits, 0, temperature, mask_class, class_masks, seeds, offsets, tau)
+        nchunk = C.sample_workspace_floats(1, V) // 2
+        return (workspace[:rows * nchunk].view(rows, nchunk),
+                workspace[rows * nchunk:2 * rows * nchunk].view(torch.int32).view(rows, nchunk))
+    toks, keys = ref.sample(logits, temperature, mask_class, class_masks, seeds, offsets, None, 0,
+                            return_keys=True, tau=tau)
+    toks = torch.where(torch.isinf(keys) & (keys < 0), torch.full_like(toks, NO_TOKEN), toks)
+    return keys.view(rows, 1), toks.view(rows, 1)
+
+
+def spec_verify(part_k, part_i, forced, input_ids, logit_rows, run_first, run_len,
+                out_tokens: Optional[torch.Tensor] = None, accept_len: Optional[torch.Tensor] = None):
+    """Final merge of the sampler's partials plus draft verification (csrc/ops/spec_verify.hip):
+    out_tokens[row] = forced[row] if >= 0, else the id of the row's best partial (larger key,
+    equal keys by smaller id; 0 when the row has no allowed token). Rows [first, first + len) of a
+    run belong to one drafting request; the draft token row j verifies is the input id of row
+    j + 1, input_ids[logit_rows[first + j + 1]]. accept_len[first] = 1 + the number of leading
+    rows whose token equals their draft token, 0 on the run's other rows; a plain row is a run of
+    length 1 and gets 1. A descriptor that is not a valid run makes the row a run of its own.
+    Returns (out_tokens, accept_len), int32 [rows]."""
+    rows = part_k.shape[0]
+    dev = part_k.device
+    out_tokens = torch.empty(rows, dtype=torch.int32, device=dev) if out_tokens is None else out_tokens
+    accept_len = torch.empty(rows, dtype=torch.int32, device=dev) if accept_len is None else accept_len
+    if _on_gpu(part_k):
+        require_native().spec_verify(out_tokens, accept_len, part_k, part_i, forced, input_ids, logit_rows,
+                                     run_first, run_len)
+        return out_tokens, accept_len
+    toks, acc = ref.spec_verify(part_k, part_i, forced, input_ids, logit_rows, run_first, run_len)
+    out_tokens[:rows].copy_(toks)
+    accept_len[:rows].copy_(acc)
+    return out_tokens, accept_len
+
+
 LOGPROB_TOP = 20             # alternatives per token the log-probability pass can return
 TOKEN_LOGPROBS_LAUNCHES = 2  # kernels token_logprobs() launches on the GPU (chunk pass + row merge)
 

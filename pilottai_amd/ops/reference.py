@@ -236,6 +236,51 @@ def sample(logits: torch.Tensor, temperature, mask_class, class_masks, seeds, of
     return (toks, keys_out) if return_keys else toks
 
 
+def spec_verify(part_k, part_i, forced, input_ids, logit_rows, run_first, run_len):
+    """Final merge of the sampler's partials plus draft verification (csrc/ops/spec_verify.hip),
+    plain Python over the rows. part_k fp32 / part_i int32 [rows, nchunk]; the other arguments
+    hold at least `rows` int32 entries, input_ids the step's token ids. Returns (tokens,
+    accept_len), int32 [rows]:
+      tokens[r]     forced[r] if >= 0, else the id of the best partial (larger key, equal keys by
+                    smaller id), 0 when that id is 0x7fffffff (no allowed token);
+      accept_len[r] for the first row of a run, 1 + the number of leading rows j of the run whose
+                    token equals the input id of row j + 1 (input_ids[logit_rows[r + j + 1]]; a
+                    logit row outside input_ids ends the count); 0 for the run's other rows.
+    A (first, len) pair that is not a valid run containing its row (first outside [0, r], r outside
+    the run, the run past `rows`, len < 1) makes the row a run of length 1."""
+    pk = part_k.detach().cpu().float().numpy()
+    pi = part_i.detach().cpu().numpy()
+    rows = pk.shape[0]
+    fc = forced.detach().cpu().numpy()
+    ids = input_ids.detach().cpu().numpy()
+    lr = logit_rows.detach().cpu().numpy()
+    rf = run_first.detach().cpu().numpy()
+    rl = run_len.detach().cpu().numpy()
+    toks = np.zeros(rows, dtype=np.int32)
+    for r in range(rows):
+        bk, bi = -np.inf, 0x7FFFFFFF
+        for c in range(pk.shape[1]):
+            k, i = float(pk[r, c]), int(pi[r, c])
+            if k > bk or (k == bk and i < bi):
+                bk, bi = k, i
+        toks[r] = int(fc[r]) if fc[r] >= 0 else (0 if bi == 0x7FFFFFFF else bi)
+    acc = np.zeros(rows, dtype=np.int32)
+    for r in range(rows):
+        first, n = int(rf[r]), int(rl[r])
+        if first < 0 or first > r or n < 1 or n > rows - first or r - first >= n:
+            first, n = r, 1
+        if first != r:
+            continue
+        a = 0
+        while a + 1 < n:
+            row = int(lr[r + a + 1])
+            if row < 0 or row >= ids.shape[0] or int(ids[row]) != int(toks[r + a]):
+                break
+            a += 1
+        acc[r] = a + 1
+    return torch.from_numpy(toks), torch.from_numpy(acc)
+
+
 def token_logprobs(logits: torch.Tensor, tokens, lp_n, forced, mask_class, class_masks, top: int = 20):
     """Per-token log-probabilities (fp64 math, sort based): log softmax(logits) over the tokens
     the row's mask class allows, at temperature 1.

@@ -225,6 +225,36 @@ def _wire_logprobs(entries: List[Dict[str, Any]]) -> Dict[str, Any]:
     return {"content": [dict(one(e), top_logprobs=[one(t) for t in e.get("top_logprobs", [])]) for e in entries]}
 
 
+def _prediction(body: Dict[str, Any]) -> Dict[str, Any]:
+    """OpenAI's Predicted Outputs (`prediction`: {"type": "content", "content": text or a list of
+    {"type": "text", "text": ...} parts, concatenated}) and the `prompt_lookup` extension, as
+    response_format entries; {} when the request asks for neither. ValueError -> 400."""
+    out: Dict[str, Any] = {}
+    pred = body.get("prediction")
+    if pred is not None:
+        if not isinstance(pred, dict) or pred.get("type") != "content":
+            raise ValueError('prediction must be an object of type "content"')
+        content = pred.get("content")
+        if isinstance(content, list):
+            parts = []
+            for part in content:
+                if not isinstance(part, dict) or part.get("type") != "text" or not isinstance(part.get("text"), str):
+                    raise ValueError('prediction.content parts must be {"type": "text", "text": string}')
+                parts.append(part["text"])
+            content = "".join(parts)
+        if not isinstance(content, str):
+            raise ValueError("prediction.content must be a string or a list of text parts")
+        if content:
+            out["prediction"] = content
+    pl = body.get("prompt_lookup")
+    if pl is not None:
+        if not isinstance(pl, bool):
+            raise ValueError("prompt_lookup must be a boolean")
+        if pl:
+            out["prompt_lookup"] = True
+    return out
+
+
 def _tools(body: Dict[str, Any]) -> Optional[List[Dict[str, Any]]]:
     tools = body.get("tools")
     if not tools:
@@ -277,8 +307,24 @@ def create_app(llm, model_name: Optional[str] = None, engine=None) -> FastAPI:
             rep = _repetition(body)
             eng = engine or getattr(llm, "engine", None)
             shaping = _shaping(body, getattr(getattr(eng, "model_cfg", None), "vocab_size", None))
+            drafts = _prediction(body)
         except (KeyError, ValueError) as e:
             raise HTTPException(400, str(e))
+        if drafts:
+            if not getattr(llm, "supports_prediction", False):
+                raise HTTPException(400, f"the {getattr(llm, 'provider', 'configured')} backend cannot use "
+                                         "a prediction / prompt_lookup")
+            if n_lp >= 0 or pens or rep:
+                raise HTTPException(400, "prediction / prompt_lookup cannot be combined with logprobs, "
+                                         "presence / frequency penalties or a repetition_penalty")
+            if eng is not None and (eng.tp.size > 1 or eng.cfg.async_steps):
+                raise HTTPException(400, "prediction / prompt_lookup are not supported on a tensor-parallel "
+                                         "or async_steps engine")
+            tok = getattr(llm, "tok", None)
+            if tok is not None and eng is not None and "prediction" in drafts and \
+                    len(tok.encode(drafts["prediction"])) > eng.max_model_len:
+                raise HTTPException(400, f"prediction is longer than max_model_len ({eng.max_model_len} tokens)")
+            rf = dict(rf or {}, **drafts)
         if shaping:
             if not getattr(llm, "supports_logit_shaping", False):
                 raise HTTPException(400, f"the {getattr(llm, 'provider', 'configured')} backend cannot apply "
