@@ -15,6 +15,8 @@ int pa_rope_cache(void* q_out, void* k_cache, void* v_cache, const void* qkv, co
                   int block_size, int apply_rope, hipStream_t st);
 int pa_kv_copy(void* k_cache, void* v_cache, const int* n_copies, const int* copies, int max_copies,
                int layers, int num_blocks, int KV, long layer_stride, int block_size, hipStream_t st);
+int pa_span_pool(const void* hn, const int* n_seg, const int* segs, int cap, float* pool, int T, int d, int slots,
+                 hipStream_t st);
 int pa_silu_mul(void* out, const void* in, int T, int F, hipStream_t st);
 int pa_paged_attention(void* out, float* part_o, float* part_ml, const void* q, const void* k_cache,
                        const void* v_cache, const int* items, const int* n_items, int max_items,
@@ -233,6 +235,27 @@ void kv_copy(at::Tensor k_cache, at::Tensor v_cache, at::Tensor n_copies, at::Te
                       (int)max_copies, (int)layers, (int)blocks, (int)KV, (long)(blocks * KV * 2048), 16,
                       cur_stream()),
            "kv_copy");
+}
+
+// hn [T, d] bf16; n_seg: one device word; segs: device words (first_row, n_rows, slot, init) x capacity;
+// pool [slots, d] fp32 accumulators (csrc/ops/span_pool.hip)
+void span_pool(at::Tensor hn, at::Tensor n_seg, at::Tensor segs, at::Tensor pool) {
+  check_gpu(hn, "hn"); check_gpu(n_seg, "n_seg"); check_gpu(segs, "segs"); check_gpu(pool, "pool");
+  check_dtype(hn, at::kBFloat16, "hn"); check_dtype(n_seg, at::kInt, "n_seg");
+  check_dtype(segs, at::kInt, "segs"); check_dtype(pool, at::kFloat, "pool");
+  TORCH_CHECK(hn.dim() == 2 && pool.dim() == 2, "span_pool: hn must be [T, d] and pool [slots, d]");
+  const int64_t T = hn.size(0), d = hn.size(1), slots = pool.size(0);
+  TORCH_CHECK_VALUE(d % 8 == 0, "span_pool: the row length ", d, " must be a multiple of 8 (16-byte loads)");
+  TORCH_CHECK(pool.size(1) == d, "span_pool: pool rows have ", pool.size(1), " entries, hn rows ", d);
+  TORCH_CHECK(n_seg.numel() >= 1, "n_seg: one int32 word");
+  const int64_t cap = segs.numel() / 4;
+  TORCH_CHECK(cap >= 1 && cap < (1ll << 31), "segs: 4 x [1, 2^31) int32 words");
+  TORCH_CHECK(T < (1ll << 31) && slots < (1ll << 31) && d <= 65535ll * 1024, "span_pool: shape too large");
+  TORCH_CHECK((uintptr_t)hn.data_ptr() % 16 == 0 && (uintptr_t)pool.data_ptr() % 16 == 0,
+              "span_pool: hn and pool must be 16-byte aligned");
+  check_rc(pa_span_pool(hn.data_ptr(), n_seg.data_ptr<int>(), segs.data_ptr<int>(), (int)cap, pool.data_ptr<float>(),
+                        (int)T, (int)d, (int)slots, cur_stream()),
+           "span_pool");
 }
 
 void silu_mul(at::Tensor out, at::Tensor in) {
@@ -1473,6 +1496,7 @@ PYBIND11_MODULE(_C, m) {
   m.def("sample_workspace_floats", &sample_workspace_floats);
   m.def("patch_pending_ids", &patch_pending_ids);
   m.def("kv_copy", &kv_copy);
+  m.def("span_pool", &span_pool);
   m.def("sample_partials", &sample_partials, py::arg("workspace"), py::arg("logits"), py::arg("vocab_offset"),
         py::arg("temperature"), py::arg("mask_class"), py::arg("class_masks"), py::arg("seeds"),
         py::arg("offsets"), py::arg("tau") = py::none());

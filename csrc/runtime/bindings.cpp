@@ -235,6 +235,7 @@ PYBIND11_MODULE(_runtime, m) {
         if (d.contains("decode_part_target")) c.decode_part_target = d["decode_part_target"].cast<int32_t>();
         if (d.contains("small_step_target")) c.small_step_target = d["small_step_target"].cast<int32_t>();
         if (d.contains("penalty_slots")) c.penalty_slots = d["penalty_slots"].cast<int32_t>();
+        if (d.contains("embed_span_slots")) c.embed_span_slots = d["embed_span_slots"].cast<int32_t>();
         if (d.contains("eos_ids")) c.eos_ids = d["eos_ids"].cast<std::vector<int32_t>>();
         return std::make_unique<Scheduler>(c);
       }))
@@ -262,6 +263,8 @@ PYBIND11_MODULE(_runtime, m) {
         d["score_target"] = L.score_target; d["score_total"] = L.score_total;
         d["n_copies"] = L.n_copies; d["copy_list"] = L.copy_list; d["copy_total"] = L.copy_total;
         d["run_first"] = L.run_first; d["run_len"] = L.run_len; d["spec_total"] = L.spec_total;
+        d["span_n"] = L.span_n; d["span_segs"] = L.span_segs; d["span_slots"] = L.span_slots;
+        d["span_total"] = L.span_total;
         d["total"] = L.total;
         return d;
       })
@@ -273,12 +276,12 @@ PYBIND11_MODULE(_runtime, m) {
               float frequency_penalty, const std::vector<std::pair<int32_t, float>>& logit_bias,
               float min_p, float ln_min_p, float repetition_penalty, float inv_repetition_penalty,
               int32_t score_from, const std::vector<int32_t>& prediction, bool prompt_lookup,
-              int32_t draft_len) {
+              int32_t draft_len, const std::vector<std::pair<int32_t, int32_t>>& spans) {
              s.add_request(id, prompt, temperature, max_tokens, seed, ignore_eos, stop_ids,
                            make_grammar(grammar), top_k, top_p, embed, embed_last, logprobs,
                            presence_penalty, frequency_penalty, logit_bias, min_p, ln_min_p,
                            repetition_penalty, inv_repetition_penalty, score_from, prediction,
-                           prompt_lookup, draft_len);
+                           prompt_lookup, draft_len, spans);
            },
            py::arg("id"), py::arg("prompt"), py::arg("temperature"), py::arg("max_tokens"),
            py::arg("seed"), py::arg("ignore_eos"), py::arg("stop_ids"), py::arg("grammar"),
@@ -289,7 +292,7 @@ PYBIND11_MODULE(_runtime, m) {
            py::arg("ln_min_p") = 0.0f, py::arg("repetition_penalty") = 1.0f,
            py::arg("inv_repetition_penalty") = 0.0f, py::arg("score_from") = -1,
            py::arg("prediction") = std::vector<int32_t>{}, py::arg("prompt_lookup") = false,
-           py::arg("draft_len") = 0)
+           py::arg("draft_len") = 0, py::arg("spans") = std::vector<std::pair<int32_t, int32_t>>{})
       // words: the buffer's size in 32-bit words (0 = not stated: steps of requests with a
       // repetition penalty, which write behind layout()["total"], are then refused)
       .def("schedule", [](Scheduler& s, uintptr_t buf, int32_t words) {
@@ -328,6 +331,10 @@ PYBIND11_MODULE(_runtime, m) {
         return l;
       })
       .def("planned_draft", &Scheduler::planned_draft)
+      .def_property_readonly_static("COUNTS9_SPAN_BIT", [](const py::object&) { return (int)COUNTS9_SPAN_BIT; })
+      // [(id, [span slot per span])] of the span requests finished or aborted since the last call
+      .def("take_span_finishes", &Scheduler::take_span_finishes)
+      .def_property_readonly("num_free_span_slots", &Scheduler::num_free_span_slots)
       .def_property_readonly_static("LOGPROB_RECORD_WORDS",
                                     [](const py::object&) { return (int)(sizeof(LogprobRecord) / 4); })
       .def_property_readonly_static("SCORE_RECORD_WORDS",

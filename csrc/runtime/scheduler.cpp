@@ -100,6 +100,11 @@ Scheduler::Scheduler(const SchedulerConfig& cfg)
   L.run_first = take(L.max_seqs);
   L.run_len = take(L.max_seqs);
   L.spec_total = o;
+  L.span_slots = std::max(0, cfg.embed_span_slots);
+  L.span_n = take(1);
+  L.span_segs = take(4 * L.span_slots);
+  L.span_total = o;
+  for (int32_t r = L.span_slots; r-- > 0;) span_free_.push_back(r);
   for (int32_t r = L.max_seqs; r-- > 0;) embed_free_.push_back(r);
   for (int32_t r = std::max(0, std::min(cfg.max_num_seqs, cfg.penalty_slots)); r-- > 0;) pen_free_.push_back(r);
 }
@@ -112,7 +117,22 @@ void Scheduler::add_request(int64_t id, std::vector<int32_t> prompt, float tempe
                             std::vector<std::pair<int32_t, float>> logit_bias, float min_p,
                             float ln_min_p, float repetition_penalty, float inv_repetition_penalty,
                             int32_t score_from, std::vector<int32_t> prediction, bool prompt_lookup,
-                            int32_t draft_len) {
+                            int32_t draft_len, std::vector<std::pair<int32_t, int32_t>> spans) {
+  if (!spans.empty()) {
+    // like a scoring request's positions, nothing of a span may be dropped or moved silently
+    if (!embed || embed_last || score_from != -1)
+      throw std::invalid_argument("scheduler: spans belong to a mean-pooled embedding request");
+    if ((int32_t)prompt.size() >= cfg_.max_model_len)
+      throw std::invalid_argument("scheduler: a request with spans needs a prompt shorter than max_model_len");
+    if ((int32_t)spans.size() > lay_.span_slots)
+      throw std::invalid_argument("scheduler: more spans than embed_span_slots");
+    if (lay_.rep_cap >= (1 << 26))
+      throw std::invalid_argument("scheduler: spans need max_num_batched_tokens + max_model_len < 2^26");
+    for (size_t i = 0; i < spans.size(); ++i)
+      if (spans[i].first < 0 || spans[i].first >= spans[i].second || spans[i].second > (int32_t)prompt.size() ||
+          (i > 0 && spans[i].first < spans[i - 1].first))
+        throw std::invalid_argument("scheduler: spans must be ranges 0 <= a < b <= prompt_len sorted by a");
+  }
   draft_len = std::max(0, std::min(draft_len, MAX_DRAFT_LEN));
   const bool drafting = draft_len > 0 && (!prediction.empty() || prompt_lookup);
   if (drafting) {
@@ -200,6 +220,10 @@ void Scheduler::add_request(int64_t id, std::vector<int32_t> prompt, float tempe
     s->draft_len = draft_len;
     ++draft_live_;
   }
+  if (!spans.empty()) {
+    s->spans = std::move(spans);
+    span_requested_ = true;
+  }
   s->arrival = arrival_counter_++;
   // a grammar that starts with forced text (e.g. '{"key": ') is jump-forwarded into the prompt
   if (s->grammar) {
@@ -229,6 +253,10 @@ void Scheduler::free_seq(Sequence* s, bool keep_embed_slot) {
   if (s->embed_slot >= 0 && !keep_embed_slot) {
     embed_free_.push_back(s->embed_slot);
     s->embed_slot = -1;
+  }
+  if (!keep_embed_slot) {  // recycled without clearing: the next holder's first segment has init = 1
+    span_free_.insert(span_free_.end(), s->span_slots.begin(), s->span_slots.end());
+    s->span_slots.clear();
   }
   drop_copy(s);
   for (int32_t b : s->blocks) bm_.release(b);
@@ -437,6 +465,9 @@ int32_t Scheduler::schedule(int32_t* buf, int32_t buf_words) {
   if (score_requested_ && buf_words < L.score_total)
     throw std::invalid_argument("scheduler: a scoring request needs a step buffer of "
                                 "layout().score_total words, stated as schedule()'s second argument");
+  if (span_requested_ && buf_words < L.span_total)
+    throw std::invalid_argument("scheduler: a request with spans needs a step buffer of "
+                                "layout().span_total words, stated as schedule()'s second argument");
   copies_ok_ = buf_words >= L.copy_total;
   drafts_ok_ = buf_words >= L.spec_total && plans_.empty();
   last_plan_.clear();
@@ -668,6 +699,12 @@ int32_t Scheduler::schedule(int32_t* buf, int32_t buf_words) {
         continue;
       }
     }
+    // a span request without enough free span slots waits (the requests behind it do not)
+    if (s->span_slots.empty() && s->spans.size() > span_free_.size()) {
+      waiting_.pop_front();
+      deferred.push_back(s);
+      continue;
+    }
     if (s->embed && s->embed_slot < 0) {
       if (embed_free_.empty()) break;  // every pooling row is in use: wait
       s->embed_slot = embed_free_.back();
@@ -739,6 +776,11 @@ int32_t Scheduler::schedule(int32_t* buf, int32_t buf_words) {
       s->pen_fresh = true;
       s->rep_fresh = true;
     }
+    if (s->span_slots.empty())
+      for (size_t i = 0; i < s->spans.size(); ++i) {
+        s->span_slots.push_back(span_free_.back());
+        span_free_.pop_back();
+      }
     pair_used += pairs;
     rep_used += reps;
     s->running = true;
@@ -858,6 +900,10 @@ int32_t Scheduler::schedule(int32_t* buf, int32_t buf_words) {
   int32_t* rfi = buf + L.run_first;
   int32_t* rln = buf + L.run_len;
 
+  // span pooling: the segment region is written only when a span has rows in the step
+  int32_t* sps = buf + L.span_segs;
+  int32_t nspan = 0;
+
   int32_t T = 0, ns = 0, nsamp = 0, nit = 0, nparted = 0, pslot = 0;
   // decode partition size: with few decode rows, 256-key flash-decoding partitions
   // give the attention launch more workgroups. 128-key partitions lose more to the
@@ -971,6 +1017,19 @@ int32_t Scheduler::schedule(int32_t* buf, int32_t buf_words) {
       er[T + j] = (s->embed_last && ppos + 1 != (int32_t)s->tokens.size()) ? L.max_seqs : erow;
     }
     if (s->embed_slot >= 0) nembed += n;
+    // the chunk's rows inside each span: one segment for the span's slot, re-initialising it
+    // when the rows start at the span's first token
+    for (size_t i = 0; i < s->span_slots.size(); ++i) {
+      const int32_t lo = std::max(s->spans[i].first, c0), hi = std::min(s->spans[i].second, ctx);
+      if (lo >= hi) continue;
+      if (nspan >= L.span_slots || buf_words < L.span_total)  // one segment per held slot at most
+        throw std::logic_error("scheduler: span segments overflow the step buffer");
+      int32_t* q = sps + 4 * nspan++;
+      q[0] = T + (lo - c0);
+      q[1] = hi - lo;
+      q[2] = s->span_slots[i];
+      q[3] = lo == s->spans[i].first ? 1 : 0;
+    }
     const int32_t nb = (ctx + B - 1) / B;
     std::memcpy(bt + (size_t)ns * L.max_blocks, s->blocks.data(), sizeof(int32_t) * nb);
     if (s->copy_j > 0) {
@@ -1254,6 +1313,10 @@ int32_t Scheduler::schedule(int32_t* buf, int32_t buf_words) {
     }
     ++stat_draft_steps_;
   }
+  if (nspan > 0) {  // ... span segments (span pooling pass): bit 28
+    counts[9] |= COUNTS9_SPAN_BIT;
+    buf[L.span_n] = nspan;
+  }
   counts[10] = npair;            // words of the pair region those rows use
   counts[11] = any_shape ? 1 + nbias : 0;  // a shaped sampling row (logit_bias / min_p pass) + its bias words
   if (nit > L.max_items)  // by construction (psz guard above, max_items sizing) this cannot happen
@@ -1324,6 +1387,11 @@ SeqOutput Scheduler::finish(Sequence* s, int32_t reason, double now) {
     o.prediction_matched = s->prediction_matched;
     draft_counts_.push_back({s->id, s->draft_proposed, s->draft_accepted, s->prediction_matched});
     s->draft_len = 0;  // counted once
+  }
+  if (!s->span_slots.empty()) {
+    // a caller that never takes the records loses the oldest instead of growing the list
+    if (span_finishes_.size() >= kMaxSpanFinishes) span_finishes_.erase(span_finishes_.begin());
+    span_finishes_.emplace_back(s->id, s->span_slots);
   }
   o.score_from = s->score_from;
   o.score_n = s->score_n;
@@ -1572,6 +1640,12 @@ std::vector<int32_t> Scheduler::take_embed_resets() {
 std::vector<Scheduler::DraftCounts> Scheduler::take_draft_counts() {
   std::vector<DraftCounts> r;
   r.swap(draft_counts_);
+  return r;
+}
+
+std::vector<std::pair<int64_t, std::vector<int32_t>>> Scheduler::take_span_finishes() {
+  std::vector<std::pair<int64_t, std::vector<int32_t>>> r;
+  r.swap(span_finishes_);
   return r;
 }
 

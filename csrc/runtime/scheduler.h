@@ -95,6 +95,9 @@ struct SchedulerConfig {
   // repetition penalty's seen set (csrc/ops/repetition.hip): a request with either holds one
   // from admission to finish; min(max_num_seqs, penalty_slots) exist
   int32_t penalty_slots = 64;
+  // device accumulator rows for span pooling (csrc/ops/span_pool.hip): an embedding request with
+  // spans holds one per span from admission to finish
+  int32_t embed_span_slots = 256;
   std::vector<int32_t> eos_ids;
 };
 
@@ -162,10 +165,26 @@ struct StepLayout {
   int32_t run_first;  // [max_seqs]
   int32_t run_len;    // [max_seqs]
   int32_t spec_total;
+  // span pooling (embedding requests with spans; csrc/ops/span_pool.hip), behind spec_total:
+  // written and copied only by steps in which a span has rows, which set bit 28 of counts[9].
+  // span_n is the step's segment count, span_segs that many (first row of the step, rows, span
+  // slot, init) quadruples: the rows of one scheduled chunk that lie inside one span, init = 1
+  // when they start at the span's first token. A span contributes at most one segment per step,
+  // so embed_span_slots quadruples always suffice. spec_total and everything before it keep their
+  // values; span_total is the whole buffer, and schedule() refuses a request with spans unless
+  // the buffer is stated to be that long.
+  int32_t span_n;     // [1]
+  int32_t span_segs;  // [4 * span_slots]
+  int32_t span_slots;
+  int32_t span_total;
 };
 
 constexpr int32_t COUNTS9_SCORE_BIT = 1 << 30;  // counts[9]: the step has scoring rows
 constexpr int32_t COUNTS9_SPEC_BIT = 1 << 29;   // counts[9]: the step has draft rows (above the repetition words)
+// counts[9]: the step has span segments. The repetition words above bit 1 count at most
+// rep_cap = max_num_batched_tokens + max_model_len tokens: they stay below bit 28 while that is
+// under 2^26, and add_request refuses spans on a scheduler configured beyond it.
+constexpr int32_t COUNTS9_SPAN_BIT = 1 << 28;
 constexpr int32_t MAX_DRAFT_LEN = 8;            // draft tokens of one run (add_request clamps draft_len)
 
 constexpr int32_t LOGIT_BIAS_MAX = 300;  // entries of one request's logit_bias
@@ -296,6 +315,12 @@ struct Sequence {
   // final hidden state is summed into pooling row embed_slot), nothing is sampled
   bool embed = false;
   int32_t embed_slot = -1;
+  // spans [a, b) over the prompt, sorted by a (overlap allowed): every scheduled chunk lists, per
+  // span, its rows inside the span as one segment for the span's slot. span_slots is empty until
+  // admission and is kept across preemption: the request restarts at token 0, so every span meets
+  // its first token -- and with it the segment that re-initialises the slot -- again.
+  std::vector<std::pair<int32_t, int32_t>> spans;
+  std::vector<int32_t> span_slots;
   // partial-block reuse: the first copy_j slots of block copy_dst (the sequence's own) come from
   // block copy_src, on which the sequence holds a reference until the step that first runs it
   // has listed the copy; copy_j = 0: none pending
@@ -339,7 +364,12 @@ class Scheduler {
                    // tokens proposed per step (0 = off, at most MAX_DRAFT_LEN). A request with a
                    // draft source and draft_len > 0 takes no logprobs, penalties, score_from or embed
                    // (std::invalid_argument); without a source, or with draft_len 0, nothing changes
-                   std::vector<int32_t> prediction = {}, bool prompt_lookup = false, int32_t draft_len = 0);
+                   std::vector<int32_t> prediction = {}, bool prompt_lookup = false, int32_t draft_len = 0,
+                   // token ranges [a, b) of an embedding request's prompt (mean pooling only), each
+                   // pooled into a span slot of its own beside the whole-prompt row: 0 <= a < b <=
+                   // prompt_len, sorted by a, at most embed_span_slots of them, a prompt shorter than
+                   // max_model_len; anything else throws std::invalid_argument
+                   std::vector<std::pair<int32_t, int32_t>> spans = {});
   bool abort(int64_t id);
   // Fill `buf` (layout()) for the next step. Returns the number of tokens in the
   // step (0 = nothing to run).
@@ -362,6 +392,8 @@ class Scheduler {
   // request with a repetition penalty gets an error, never a write past its buffer.
   // The same holds one region further for scoring requests: once one has been added, schedule()
   // throws unless buf_words >= layout().score_total.
+  // And one further for spans: once a request with spans has been added, schedule() throws unless
+  // buf_words >= layout().span_total.
   // Drafts are planned only into a buffer stated to hold layout().spec_total words, and never
   // while a step is in flight (pipelined use): otherwise a drafting request decodes plainly.
   int32_t schedule(int32_t* buf, int32_t buf_words = 0);
@@ -392,6 +424,12 @@ class Scheduler {
     int32_t proposed, accepted, matched;
   };
   std::vector<DraftCounts> take_draft_counts();
+  // The finish records of span requests: (id, the accumulator row of each span in the request's
+  // span order) of those finished or aborted since the last call. After FINISH_EMBED the rows
+  // hold the sums: read them before the next step is scheduled. Take the records every step; the
+  // list keeps the newest kMaxSpanFinishes.
+  static constexpr size_t kMaxSpanFinishes = 4096;
+  std::vector<std::pair<int64_t, std::vector<int32_t>>> take_span_finishes();
   // the draft of the request's entry in the step scheduled last (empty: none), for diagnostics
   std::vector<int32_t> planned_draft(int64_t id) const;
   // Finished-by-abort outputs are returned here as well.
@@ -426,6 +464,7 @@ class Scheduler {
   std::vector<SeqState> debug_state() const;  // every live sequence (diagnostics)
   int32_t num_free_embed_rows() const { return (int32_t)embed_free_.size(); }
   int32_t num_free_penalty_slots() const { return (int32_t)pen_free_.size(); }
+  int32_t num_free_span_slots() const { return (int32_t)span_free_.size(); }
 
  private:
   bool ensure_blocks(Sequence* s, int32_t upto_tokens);
@@ -484,6 +523,9 @@ class Scheduler {
   std::vector<int32_t> embed_free_;    // free pooling rows (0 .. max_seqs - 1)
   std::vector<int32_t> embed_resets_;  // rows of preempted embedding requests, to be cleared
   std::vector<int32_t> pen_free_;      // free penalty slots
+  std::vector<int32_t> span_free_;     // free span slots
+  bool span_requested_ = false;        // a request with spans was added: see schedule() (the buffer's size)
+  std::vector<std::pair<int64_t, std::vector<int32_t>>> span_finishes_;
   bool rep_requested_ = false;         // a request with a repetition penalty was added: see schedule()
   bool score_requested_ = false;       // a scoring request was added: see schedule() (the buffer's size)
   int32_t score_live_ = 0;             // scoring requests not yet finished: the row budget applies

@@ -165,6 +165,15 @@ class EngineConfig:
     # attention item; longer runs become narrow prefill items. max_draft_len bounds submit(draft_len=).
     draft_len: int = 3
     max_draft_len: int = 8
+    # span pooling (submit(embed=True, spans=[...]); csrc/ops/span_pool.hip): fp32 accumulator rows
+    # on the device, one per span of a running span request; further requests wait for free rows.
+    # The rows (slots x hidden_size x 4 bytes, 4 MB at 256 x 4,096) are allocated on the first such step.
+    embed_span_slots: int = 256
+    # True: a step that pools spans runs its mid / prefill route "ordered" (LlamaModel._forward_mid),
+    # so that the rows the spans sum, and with them the span means, are the same bits from run to
+    # run, eager or replayed; about 10 % of such a step. False: such a step runs the kernels every
+    # other step runs; the span sums stay ordered, the rows they read may differ in their last bits.
+    embed_span_ordered: bool = True
 
 
 # TP step header: [op, T, ns, nsamp, bucket, masks_changed, n_copy, truncate, embed]
@@ -201,6 +210,9 @@ class GenerationOutput:
     # prediction's next one), and proposed draft tokens the sampler did not confirm; 0 otherwise
     accepted_prediction_tokens: int = 0
     rejected_prediction_tokens: int = 0
+    # submit(embed=True, spans=[(a, b), ...]): [len(spans), hidden] fp32, row i the mean final-norm
+    # hidden state of prompt tokens a_i .. b_i - 1, summed in ascending token order in fp32
+    span_embeddings: Optional[np.ndarray] = field(default=None, repr=False)
 
     @property
     def text(self) -> str:
@@ -246,6 +258,7 @@ class _Request:
     prediction: tuple = ()               # token ids the reply is expected to repeat (draft source)
     prompt_lookup: bool = False          # n-gram drafts from the request's own tokens
     draft_len: int = 0                   # draft tokens per step; 0 = not a drafting request
+    spans: tuple = ()                    # ((a, b), ...) token ranges of an embedding request, sorted by a
 
 
 class LLMEngine:
@@ -349,6 +362,7 @@ class LLMEngine:
             "small_step_target": int(cfg.small_step_target) if small_step else 0,
             "decode_part_target": int(cfg.decode_part_target),
             "penalty_slots": max(0, min(int(cfg.max_num_seqs), int(cfg.penalty_slots))),
+            "embed_span_slots": max(0, int(cfg.embed_span_slots)),
             "eos_ids": list(self.tok.eos_ids)})
         L = self.L = self.sched.layout()
         pin = self.on_gpu
@@ -356,11 +370,11 @@ class LLMEngine:
         # one being scheduled); the device copy is stream-ordered behind the previous step
         self._async = bool(cfg.async_steps) and self.tp.size == 1
         nbuf = 2 if self._async else 1
-        self._host_metas = [torch.zeros(L["spec_total"], dtype=torch.int32, pin_memory=pin) for _ in range(nbuf)]
+        self._host_metas = [torch.zeros(L["span_total"], dtype=torch.int32, pin_memory=pin) for _ in range(nbuf)]
         self._host_meta = self._host_metas[0]
         self._host_ptr = self._host_meta.data_ptr()
         self._host_np = self._host_meta.numpy()
-        self._dev_meta = torch.zeros(L["spec_total"], dtype=torch.int32, device=self.device) \
+        self._dev_meta = torch.zeros(L["span_total"], dtype=torch.int32, device=self.device) \
             if (self.on_gpu or self._async) else self._host_meta
         # attention tickets: one per (sequence, KV head) for split decode rows, then -- only with
         # prefill_split_keys on -- one per (partial slot, KV head) for split prefill items
@@ -440,6 +454,13 @@ class LLMEngine:
         self._accept_dev = torch.zeros(S4, dtype=torch.int32, device=self.device)
         self._accept_hosts = [torch.zeros(S, dtype=torch.int32, pin_memory=pin) for _ in range(nbuf)]
         self._draft_counts: Dict[int, tuple] = {}  # request id -> (proposed, accepted, prediction matched)
+        # span pooling (submit(embed=True, spans=)): ops.span_pool runs right behind the whole-prompt
+        # pooling in the step graph's span variant, on the same final-norm rows, and adds each
+        # listed segment into its span's accumulator row; the rows of a request are read at the
+        # commit that finishes it. Allocated on the first step that has a segment.
+        self._span_bit = int(self._rt.Scheduler.COUNTS9_SPAN_BIT)
+        self._span_pool = None
+        self._span_ready: Dict[int, np.ndarray] = {}  # request id -> span means read at its step's commit
         # presence / frequency penalties (submit(presence_penalty=, frequency_penalty=)): per-slot
         # token counts on the device, allocated on the first penalised request; ops.apply_penalties
         # rewrites the logits behind the LM head in the step graph's penalty variant
@@ -457,7 +478,8 @@ class LLMEngine:
         # logit_bias / min_p row the 6-tuple key (bucket, trunc, embed, lp, pen, True), a step
         # with a repetition-penalty row the 7-tuple key (bucket, trunc, embed, lp, pen, shape, True),
         # a step with scoring rows the 8-tuple key (bucket, trunc, embed, lp, pen, shape, rep, True),
-        # a step with draft rows the 9-tuple key (bucket, trunc, embed, lp, pen, shape, rep, score, True).
+        # a step with draft rows the 9-tuple key (bucket, trunc, embed, lp, pen, shape, rep, score, True),
+        # a step with span segments the 10-tuple key (..., score, spec, True).
         self._graphs: Dict[tuple, "torch.cuda.CUDAGraph"] = {}
         self._tau = torch.empty(S, dtype=torch.float32, device=self.device)
         self._graph_pool = None
@@ -571,6 +593,8 @@ class LLMEngine:
         self._copy_list = sl("copy_list", 3 * ms)
         self._run_first = sl("run_first", ms)
         self._run_len = sl("run_len", ms)
+        self._span_n = sl("span_n", 1)
+        self._span_segs = sl("span_segs", 4 * L["span_slots"])
 
     def _sync_masks(self) -> bool:
         reg = self.grammar.reg
@@ -603,9 +627,16 @@ class LLMEngine:
             self._rep_state = ops.repetition_state(self._pen_slots, self.model.v_local, self.max_model_len,
                                                    self.device)
 
+    def _ensure_span_state(self):
+        """Allocate the span accumulator rows (engine thread, never inside a capture). Never
+        cleared: a span's first segment starts its row from zero."""
+        if self._span_pool is None:
+            self._span_pool = torch.zeros(max(1, self.L["span_slots"]), self.model_cfg.hidden_size,
+                                          dtype=torch.float32, device=self.device)
+
     def _forward_and_sample(self, bucket: int, s_b: int, ns: int, trunc: bool = False, embed: bool = False,
                             lp: bool = False, pen: bool = False, shape: bool = False, rep: bool = False,
-                            score: bool = False, spec: bool = False):
+                            score: bool = False, spec: bool = False, span: bool = False):
         meta = self._meta_for(bucket, s_b, ns)
         if self._partial:
             # partial-block prefix hits: the cached heads go into the new blocks before any layer
@@ -613,8 +644,10 @@ class LLMEngine:
             ops.kv_copy(self.kv.k, self.kv.v, self._n_copies, self._copy_list)
         if self._async:  # pending tokens of rows that sampled in the previous step
             ops.patch_pending_ids(meta.input_ids[:bucket], self._sampled_dev)
-        logits = self.model.forward(meta, self.kv, bucket, s_b, self._part_o, self._part_ml,
-                                    embed=(self._embed_rows, self._embed_pool) if embed else None)
+        pooling = (self._embed_rows, self._embed_pool) if embed else None
+        if span:  # span steps pool: the segments are rows of embedding requests (capture_graphs)
+            pooling = pooling + ((self._span_n, self._span_segs, self._span_pool, bool(self.cfg.embed_span_ordered)),)
+        logits = self.model.forward(meta, self.kv, bucket, s_b, self._part_o, self._part_ml, embed=pooling)
         if rep:
             # on the raw logits, before the additive penalties and everything else
             ops.apply_repetition_penalty(logits, self._rep_state, self._rep_slot[:s_b], self._rep_reset[:s_b],
@@ -689,7 +722,10 @@ class LLMEngine:
 
     @staticmethod
     def _graph_key(bucket: int, trunc: bool, embed: bool, lp: bool = False, pen: bool = False,
-                   shape: bool = False, rep: bool = False, score: bool = False, spec: bool = False) -> tuple:
+                   shape: bool = False, rep: bool = False, score: bool = False, spec: bool = False,
+                   span: bool = False) -> tuple:
+        if span:
+            return (bucket, trunc, embed, lp, pen, shape, rep, score, spec, True)
         if spec:
             return (bucket, trunc, embed, lp, pen, shape, rep, score, True)
         if score:
@@ -704,28 +740,30 @@ class LLMEngine:
 
     def _run(self, bucket: int, ns: int, trunc: bool, n_copy: int, embed: bool = False, lp: bool = False,
              pen: bool = False, shape: bool = False, rep: bool = False, score: bool = False,
-             spec: bool = False):
-        """Replay the (bucket, trunc, embed[, logprobs[, penalties[, shaping[, repetition[, scoring[, drafts]]]]]]) graph
+             spec: bool = False, span: bool = False):
+        """Replay the (bucket, trunc, embed[, logprobs[, penalties[, shaping[, repetition[, scoring[, drafts[, spans]]]]]]]) graph
         — capturing it first if needed — or run eagerly."""
         if pen:
             self._ensure_pen_state()
         if rep:
             self._ensure_rep_state()
+        if span:
+            self._ensure_span_state()
         if not self.use_graphs:
             self._forward_and_sample(bucket, self._seq_bucket(bucket), ns, trunc, embed, lp, pen, shape, rep,
-                                     score, spec)
+                                     score, spec, span)
             return
-        key = self._graph_key(bucket, trunc, embed, lp, pen, shape, rep, score, spec)
+        key = self._graph_key(bucket, trunc, embed, lp, pen, shape, rep, score, spec, span)
         g = self._graphs.get(key)
         if g is None:
-            # the regions of shaped / repetition / scoring rows, the copy list and the runs lie
-            # behind the copied prefix: keep the whole buffer
-            n_copy = self.L["spec_total"]
+            # the regions of shaped / repetition / scoring rows, the copy list, the runs and the
+            # span segments lie behind the copied prefix: keep the whole buffer
+            n_copy = self.L["span_total"]
             saved = self._dev_meta[:n_copy].clone()
             pool = self._embed_pool.clone()
             samp = self._sampled_dev.clone()  # the previous step's tokens (pipelined mode)
             self.capture_graphs([bucket], trunc=trunc, embed=embed, lp=lp, pen=pen,
-                                shape=shape, rep=rep, score=score, spec=spec)  # clobbers the device metadata
+                                shape=shape, rep=rep, score=score, spec=spec, span=span)  # clobbers the device metadata
             self.stats["graph_captures"] += 1  # a first-use capture inside serving (tens of ms)
             self._dev_meta[:n_copy].copy_(saved)
             self._embed_pool.copy_(pool)
@@ -754,6 +792,13 @@ class LLMEngine:
         a, b = self.L["run_first"], self.L["run_len"] + self.L["max_seqs"]
         self._dev_meta[a:b].copy_(hm[a:b], non_blocking=self.on_gpu)
 
+    def _copy_spans(self, hm: torch.Tensor):
+        """Host -> device copy of the span region of a step with segments: the count and the
+        quadruples in use, one piece."""
+        a = self.L["span_n"]
+        b = self.L["span_segs"] + 4 * int(hm[a])
+        self._dev_meta[a:b].copy_(hm[a:b], non_blocking=self.on_gpu)
+
     def _copy_copies(self, hm: torch.Tensor, n: int):
         """Host -> device copy of the `n` partial-block copy triples of a step that has some (the
         count itself lies in the header every step copies)."""
@@ -772,7 +817,8 @@ class LLMEngine:
     def _dummy_meta(self):
         """A metadata state under which a forward touches no KV and no attention item."""
         L = self.L
-        d = torch.zeros(L["spec_total"], dtype=torch.int32)  # n_copies = 0: the copy kernel touches nothing
+        # n_copies = 0: the copy kernel touches nothing; span_n = 0: nor does the span pass
+        d = torch.zeros(L["span_total"], dtype=torch.int32)
         d[L["slots"]:L["slots"] + L["max_tokens"]] = -1
         d[L["embed_rows"]:L["embed_rows"] + L["max_tokens"]] = L["max_seqs"]
         d[L["pen_slot"]:L["pen_slot"] + L["max_seqs"]] = -1  # the penalty pass touches nothing
@@ -792,23 +838,27 @@ class LLMEngine:
 
     def capture_graphs(self, buckets: Optional[Sequence[int]] = None, trunc: bool = False, embed: bool = False,
                        lp: bool = False, pen: bool = False, shape: bool = False, rep: bool = False,
-                       score: bool = False, spec: bool = False):
+                       score: bool = False, spec: bool = False, span: bool = False):
         """Capture one hipGraph per token bucket (shared memory pool); the top-k/top-p,
         embedding-pooling, log-probability, penalty, logit_bias / min_p (`shape`), repetition
-        penalty (`rep`), prompt-scoring (`score`) and draft (`spec`) variants are captured on
-        first use, or up front by a call with the flag set."""
+        penalty (`rep`), prompt-scoring (`score`), draft (`spec`) and span-pooling (`span`) variants are captured on
+        first use, or up front by a call with the flag set. `span` implies `embed`: a step with
+        span segments always pools, so span=True alone captures the variant such a step replays."""
         if not self.use_graphs:
             return
+        embed = embed or span
         if pen:
             self._ensure_pen_state()
         if rep:
             self._ensure_rep_state()
+        if span:
+            self._ensure_span_state()
         self._dummy_meta()
         if self._graph_pool is None:
             self._graph_pool = torch.cuda.graph_pool_handle()
         t0 = time.time()
         for b in sorted(buckets or self.buckets, reverse=True):
-            key = self._graph_key(b, trunc, embed, lp, pen, shape, rep, score, spec)
+            key = self._graph_key(b, trunc, embed, lp, pen, shape, rep, score, spec, span)
             if key in self._graphs:
                 continue
             s_b = self._seq_bucket(b)
@@ -816,11 +866,11 @@ class LLMEngine:
             st.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(st):
                 for _ in range(2):
-                    self._forward_and_sample(b, s_b, 0, trunc, embed, lp, pen, shape, rep, score, spec)
+                    self._forward_and_sample(b, s_b, 0, trunc, embed, lp, pen, shape, rep, score, spec, span)
             torch.cuda.current_stream().wait_stream(st)
             g = torch.cuda.CUDAGraph(keep_graph=True) if self.cfg.keep_graphs else torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, pool=self._graph_pool):
-                self._forward_and_sample(b, s_b, 0, trunc, embed, lp, pen, shape, rep, score, spec)
+                self._forward_and_sample(b, s_b, 0, trunc, embed, lp, pen, shape, rep, score, spec, span)
             if self.cfg.keep_graphs:
                 g.instantiate()
             self._graphs[key] = g
@@ -880,7 +930,7 @@ class LLMEngine:
                frequency_penalty: float = 0.0, logit_bias: Optional[Mapping[int, float]] = None,
                min_p: float = 0.0, repetition_penalty: float = 1.0, score_from: Optional[int] = None,
                prediction: Sequence[int] = (), prompt_lookup: bool = False,
-               draft_len: Optional[int] = None) -> int:
+               draft_len: Optional[int] = None, spans: Optional[Sequence[Tuple[int, int]]] = None) -> int:
         """Thread-safe; `callback` runs on the engine thread when the request finishes.
 
         top_k > 0 / top_p < 1 truncate the (grammar-masked) distribution before
@@ -950,9 +1000,23 @@ class LLMEngine:
         rejected_prediction_tokens. A draft never preempts a request and never takes a sampling
         row from a plain decode row. draft_len without a prediction or prompt_lookup changes
         nothing. Refused: prediction ids outside the vocabulary, draft_len outside
-        [0, max_draft_len], logprobs, any penalty, score_from, embed, a TP > 1 engine, async_steps."""
+        [0, max_draft_len], logprobs, any penalty, score_from, embed, a TP > 1 engine, async_steps.
+
+        spans = [(a, b), ...] on an embed=True request: token ranges of the prompt, 0 <= a < b <=
+        len(prompt_ids), sorted by a, overlap allowed, at most EngineConfig.embed_span_slots. Beside
+        the whole-prompt `embedding` the output carries span_embeddings [len(spans), hidden] fp32:
+        row i is the mean final-norm hidden state of tokens a_i .. b_i - 1 of this prompt -- each
+        token has seen the whole prompt before it, so one prefill yields a document vector and all
+        of its chunk vectors. The bf16 rows of a span are added one by one in ascending token
+        order into an fp32 accumulator that starts at +0 (csrc/ops/span_pool.hip) and the sum is
+        divided by b - a once on the host: the bits do not depend on how the prompt was cut into
+        prefill chunks, on what it was batched with, or on the run. Refused: malformed spans, a
+        prompt of max_model_len tokens or more, spans without embed or with embed="last", a TP > 1
+        engine, async_steps (the pipelined loop reads pooling rows from per-step host snapshots,
+        which hold no span rows)."""
         if self._err is not None:
             raise RuntimeError(f"engine failed: {self._err!r}")
+        span_list = self._check_spans(spans, prompt_ids, embed, score_from)
         pred, n_draft = self._check_drafts(prediction, prompt_lookup, draft_len)
         if n_draft and score_from is not None:
             raise ValueError("prediction / prompt_lookup are not available on a scoring request")
@@ -1017,10 +1081,43 @@ class LLMEngine:
                        int(top_k or 0), float(1.0 if top_p is None else top_p), bool(embed), embed == "last",
                        logprobs, pens[0], pens[1], bias, min_p, ref_ln_min_p(min_p), rep_r,
                        ref_inv_repetition_penalty(rep_r), prediction=pred if n_draft else (),
-                       prompt_lookup=bool(prompt_lookup) and n_draft > 0, draft_len=n_draft)
+                       prompt_lookup=bool(prompt_lookup) and n_draft > 0, draft_len=n_draft, spans=span_list)
         self._inbox.put(req)
         self._wake.set()
         return rid
+
+    def _check_spans(self, spans, prompt_ids, embed, score_from) -> tuple:
+        """Validate submit()'s `spans` (None or empty: none): ((a, b), ...); ValueError for anything
+        outside the rules."""
+        if spans is None or len(spans) == 0:
+            return ()
+        if embed is not True and embed != "mean":
+            raise ValueError("spans need embed=True" if not embed or score_from is not None
+                             else 'spans are mean-pooled: embed="last" is not supported with them')
+        if score_from is not None:
+            raise ValueError("spans are not available on a scoring request")
+        if self.tp.size > 1:
+            raise ValueError("spans are not supported on a tensor-parallel (TP > 1) engine")
+        if self.cfg.async_steps:
+            raise ValueError("spans are not supported on an async_steps engine")
+        n, slots = len(prompt_ids), int(self.L["span_slots"])
+        if n >= self.max_model_len:
+            raise ValueError(f"spans: {n} tokens do not fit max_model_len {self.max_model_len}")
+        if len(spans) > slots:
+            raise ValueError(f"spans: at most embed_span_slots = {slots} per request, not {len(spans)}")
+        out, prev = [], 0
+        for sp in spans:
+            try:
+                a, b = sp
+            except (TypeError, ValueError):
+                raise ValueError(f"spans: {sp!r} is not an (a, b) pair") from None
+            if any(isinstance(v, bool) or not isinstance(v, Integral) for v in (a, b)) or not 0 <= a < b <= n:
+                raise ValueError(f"spans: {sp!r} is not a range 0 <= a < b <= {n} of integers")
+            if a < prev:
+                raise ValueError("spans must be sorted by their first token")
+            prev = a
+            out.append((int(a), int(b)))
+        return tuple(out)
 
     def _check_drafts(self, prediction, prompt_lookup, draft_len) -> Tuple[tuple, int]:
         """Validate submit()'s draft arguments: (prediction ids, draft tokens per step -- 0 when the
@@ -1172,6 +1269,15 @@ class LLMEngine:
         if bad:
             raise RuntimeError(f"embedding requests did not complete: {bad}")
         return np.stack([o.embedding for o in outs]) if outs else np.zeros((0, self.model_cfg.hidden_size), np.float32)
+
+    def embed_spans(self, prompt_ids: Sequence[int], spans: Sequence[Tuple[int, int]]) -> Tuple[np.ndarray, np.ndarray]:
+        """One embedding request with spans (submit(embed=True, spans=)): (the whole-prompt mean
+        [hidden], the span means [len(spans), hidden]), both fp32. Blocking; thread-safe."""
+        o = self.generate([list(prompt_ids)], embed=True, spans=list(spans), temperature=0.0, max_tokens=1)[0]
+        if o.embedding is None or (len(spans) and o.span_embeddings is None):
+            raise RuntimeError(f"embedding request did not complete: {o.finish_reason}")
+        se = o.span_embeddings if len(spans) else np.zeros((0, self.model_cfg.hidden_size), np.float32)
+        return o.embedding, se
 
     def prewarm(self, prompt_ids: Sequence[int], timeout: float = 300.0) -> int:
         """Compute and cache the KV of `prompt_ids` (prefix cache) without keeping
@@ -1344,7 +1450,7 @@ class LLMEngine:
                                    req.embed_last, req.logprobs, req.presence_penalty, req.frequency_penalty,
                                    list(req.logit_bias), req.min_p, req.ln_min_p, req.repetition_penalty,
                                    req.inv_repetition_penalty, req.score_from, list(req.prediction),
-                                   req.prompt_lookup, req.draft_len)
+                                   req.prompt_lookup, req.draft_len, list(req.spans))
             self.stats["requests"] += 1
         while True:
             try:
@@ -1375,6 +1481,8 @@ class LLMEngine:
         out = GenerationOutput(rid, list(toks), _REASONS.get(reason, "stop"), plen, cached, len(toks),
                                nsamp, nforced, req.t_arrival, t_first, t_fin, self.tok, emb,
                                lps, None if lps is None else float(sum(e[0] for e in lps)))
+        if req.spans:
+            out.span_embeddings = self._span_ready.pop(rid, None)
         if req.score_from >= 0:  # a scoring request's records are per prompt position: (logprob, rank, top)
             out.logprobs, out.prompt_logprobs = None, lps
         if req.draft_len > 0:
@@ -1416,7 +1524,13 @@ class LLMEngine:
         pen = (int(c[9]) & 1) > 0
         score = (int(c[9]) & self._score_bit) > 0  # the step has scoring rows
         spec = (int(c[9]) & self._spec_bit) > 0  # the step has draft rows
-        rep = (int(c[9]) & (self._spec_bit - 1)) >> 1  # 0, or 1 + 2 * the token words of the step's repetition-penalty rows
+        span = (int(c[9]) & self._span_bit) > 0  # the step has span segments
+        # 0, or 1 + 2 * the token words of the step's repetition-penalty rows. The mask ends below
+        # the lowest flag bit, which is now the span bit (28) and was the draft bit (29). Every
+        # step decodes the value it decoded before: the field holds 3 + 4 * words at most, below
+        # 2^28 while the repetition region has fewer than 2^26 words (64 M tokens per step, far
+        # above any configuration; the scheduler refuses spans otherwise), so bit 28 was clear
+        rep = (int(c[9]) & (self._span_bit - 1)) >> 1
         shape = int(c[11])  # 0, or 1 + the bias words of the step's logit_bias / min_p rows
         bucket = next(b for b in self.buckets if b >= T)
         s_b = self._seq_bucket(bucket)
@@ -1437,6 +1551,8 @@ class LLMEngine:
                 self._copy_scoring(self._host_meta)
             if spec:
                 self._copy_runs(self._host_meta)
+            if span:
+                self._copy_spans(self._host_meta)
             ncp = int(self._host_np[L["n_copies"]])
             if ncp:
                 self._copy_copies(self._host_meta, ncp)
@@ -1446,7 +1562,7 @@ class LLMEngine:
                 self.tp.broadcast(self._class_masks)
             self.tp.broadcast(self._dev_meta[:n_copy])
         with torch.inference_mode(), trace_range("engine.forward"):
-            self._run(bucket, ns, trunc, n_copy, embed, lp, pen, shape > 0, rep > 0, score, spec)
+            self._run(bucket, ns, trunc, n_copy, embed, lp, pen, shape > 0, rep > 0, score, spec, span)
         if self._step_listeners:
             self._notify_launch(T)
         if nsamp:
@@ -1474,6 +1590,8 @@ class LLMEngine:
                                      self._accept_hosts[0].data_ptr() if spec else 0)
         if embed:
             self._read_embeddings(outs)
+        if self._span_pool is not None:
+            self._read_spans(outs)
         st = self.stats
         # host-side phases: schedule, metadata copy + launch, device wait, commit
         st["host_sched_s"] += t_sched - t0
@@ -1617,6 +1735,21 @@ class LLMEngine:
         self._embed_pool.index_fill_(0, idx, 0.0)
         for (e, plen), r in zip(done, rows):
             self._embed_ready[e] = r / plen
+
+    def _read_spans(self, outs):
+        """Span means of the span requests this step finished: their accumulator rows are read
+        now, before the next step is scheduled (a finished request's slots are free again, and
+        their next holders' first segments overwrite them), and divided by the span lengths once,
+        in fp32."""
+        done = {o[0] for o in outs if o[2] == 3}
+        for rid, slots in self.sched.take_span_finishes():
+            req = self._reqs.get(rid)
+            if rid not in done or req is None or len(slots) != len(req.spans):
+                continue  # aborted: nothing to report
+            idx = torch.tensor(slots, dtype=torch.long, device=self.device)
+            sums = self._span_pool.index_select(0, idx).cpu().numpy()
+            lens = np.array([b - a for a, b in req.spans], dtype=np.float32)
+            self._span_ready[rid] = sums / lens[:, None]
 
     def _pool_div(self, rid: int, plen: int) -> int:
         """Tokens pooled into an embedding request's row: its prompt (mean), or 1 (last)."""

@@ -35,6 +35,7 @@ class OpenAICompatLLM(BaseLLM):
     supports_penalties = True
     supports_logit_shaping = True
     supports_repetition_penalty = True
+    supports_embeddings = True  # POST /v1/embeddings (OpenAI's endpoint; `chunking` is a pilottai_amd extension)
 
     def __init__(self, config: Any = None, base_url: Optional[str] = None, timeout_s: float = 600.0,
                  schema_mode: str = "pilottai"):
@@ -143,6 +144,46 @@ class OpenAICompatLLM(BaseLLM):
                          top_logprobs=[dict(a, logprob=inf(a["logprob"])) for a in t.get("top_logprobs", [])])
                     for t in s["tokens"]]
             out.append({"logprob": inf(s["logprob"]), "tokens": toks})
+        self.usage["calls"] += 1
+        self.usage["prompt_tokens"] += int((data.get("usage") or {}).get("prompt_tokens", 0))
+        return out
+
+    async def embed(self, inputs, chunking: Optional[Dict[str, int]] = None) -> List[Dict[str, Any]]:
+        """POST /v1/embeddings: one {"embedding": fp32 array, "prompt_tokens"} per input (texts or
+        token id lists), vectors sent as base64 so they arrive bit for bit. `chunking`
+        ({"chunk_tokens", "overlap"}, a pilottai_amd server's extension) adds each input's "chunks".
+        The server reports token counts only in total, so "prompt_tokens" is None here."""
+        import base64
+
+        import numpy as np
+
+        if isinstance(inputs, str) or not len(inputs):
+            raise ValueError("inputs must be a non-empty list of texts or token id lists")
+        body: Dict[str, Any] = {"model": self.model_name, "input": [x if isinstance(x, str) else list(x) for x in inputs],
+                                "encoding_format": "base64"}
+        if chunking is not None:
+            if self.schema_mode != "pilottai":
+                raise NotImplementedError("chunking is an extension of a pilottai_amd server (schema_mode 'pilottai')")
+            body["chunking"] = dict(chunking)
+        r = await self._http().post(f"{self.base_url}/embeddings", json=body)
+        if r.status_code == 404:
+            raise NotImplementedError(f"the server at {self.base_url} has no /embeddings endpoint")
+        if r.status_code == 400:
+            raise ValueError(f"HTTP 400: {r.text[:300]}")
+        if r.status_code != 200:
+            raise RuntimeError(f"HTTP {r.status_code}: {r.text[:300]}")
+        data = r.json()
+
+        def vec(v):
+            return np.frombuffer(base64.b64decode(v), dtype="<f4").astype(np.float32) if isinstance(v, str) \
+                else np.asarray(v, dtype=np.float32)
+
+        out = []
+        for d in sorted(data["data"], key=lambda d: d["index"]):
+            item: Dict[str, Any] = {"embedding": vec(d["embedding"]), "prompt_tokens": None}
+            if "chunks" in d:
+                item["chunks"] = [dict(c, embedding=vec(c["embedding"])) for c in d["chunks"]]
+            out.append(item)
         self.usage["calls"] += 1
         self.usage["prompt_tokens"] += int((data.get("usage") or {}).get("prompt_tokens", 0))
         return out

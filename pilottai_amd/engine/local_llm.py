@@ -32,7 +32,10 @@ import re
 import threading
 import time
 from collections import deque
-from typing import Any, Deque, Dict, List, Optional, Sequence, Union
+from numbers import Integral
+from typing import Any, Deque, Dict, List, Mapping, Optional, Sequence, Union
+
+import numpy as np
 
 from .tokenizer import END_HEADER_ID, EOT_ID, START_HEADER_ID, BOS_ID, Tokenizer
 
@@ -119,6 +122,16 @@ class BaseLLM:
     # response_format["prediction"] (text the reply is expected to repeat) / ["prompt_lookup"] are
     # honoured and r["usage"]["completion_tokens_details"] returned
     supports_prediction = False
+    supports_embeddings = False  # embed(): pooled final hidden states of given texts / token ids
+
+    async def embed(self, inputs: Sequence[Union[str, Sequence[int]]],
+                    chunking: Optional[Dict[str, int]] = None) -> List[Dict[str, Any]]:
+        """One {"embedding": fp32 [hidden], L2-normalised, "prompt_tokens": n} per input (a text or
+        a list of token ids). chunking = {"chunk_tokens": c, "overlap": o} adds "chunks":
+        [{"index", "span": [a, b], "text", "embedding"}], the chunk vectors computed inside the
+        document (late chunking). Backends without a model to ask refuse."""
+        raise NotImplementedError(f"the {self.provider!r} LLM backend cannot embed text "
+                                  "(supports_embeddings is False): use the local engine or a pilottai_amd server")
 
     async def score(self, messages_or_text: Union[str, Sequence[Dict[str, str]]], candidates: Sequence[str],
                     top: int = 0) -> List[Dict[str, Any]]:
@@ -232,6 +245,7 @@ class LocalLLM(BaseLLM):
     supports_repetition_penalty = True
     supports_scoring = True
     supports_prediction = True
+    supports_embeddings = True
     prefix_cache_layout = True  # agents put the shared task text first (core/agent.py)
 
     def __init__(self, config: Any = None, engine=None):
@@ -305,6 +319,93 @@ class LocalLLM(BaseLLM):
         self.usage["calls"] += 1
         self.usage["prompt_tokens"] += usage["prompt_tokens"]
         return res, usage
+
+    async def embed(self, inputs, chunking: Optional[Dict[str, int]] = None) -> List[Dict[str, Any]]:
+        """Embedding requests in the local continuous batch (engine.submit(embed=True)): the
+        L2-normalised mean final-norm hidden state of each input's tokens. Texts are tokenised as
+        they are (no begin-of-text token, like memory/embedding.EngineEmbedder); token ids must lie
+        in the vocabulary. With `chunking` every context window of the input (span_windows over
+        max_model_len - 1 tokens) is ONE span request (submit(spans=)) that yields the window's
+        vector and all of its chunk vectors, so inputs longer than the context are allowed; the
+        input's own vector is then the token-weighted mean of its windows' (the overlap tokens
+        between two windows count in both). ValueError for anything outside these rules."""
+        from pilottai_amd.memory.embedding import span_windows
+
+        eng = self.engine
+        if isinstance(inputs, str) or not isinstance(inputs, Sequence) or not len(inputs):
+            raise ValueError("inputs must be a non-empty list of texts or token id lists")
+        c = o = None
+        if chunking is not None:
+            if not isinstance(chunking, Mapping) or set(chunking) - {"chunk_tokens", "overlap"}:
+                raise ValueError('chunking must be {"chunk_tokens": n, "overlap": m}')
+            c, o = chunking.get("chunk_tokens"), chunking.get("overlap", 0)
+            if eng.tp.size > 1 or eng.cfg.async_steps:
+                raise ValueError("chunking is not supported on a tensor-parallel or async_steps engine")
+        V = eng.model_cfg.vocab_size
+        jobs = []  # (input index, ids, window start, [(a, b)] in window coordinates)
+        all_ids, spans_of = [], []
+        for i, x in enumerate(inputs):
+            if isinstance(x, str):
+                ids = self.tok.encode(x)
+            elif isinstance(x, Sequence):
+                ids = list(x)
+                for t in ids:
+                    if isinstance(t, bool) or not isinstance(t, Integral) or not 0 <= t < V:
+                        raise ValueError(f"input {i}: token id {t!r} is not an integer in [0, {V})")
+            else:
+                raise ValueError(f"input {i} is neither a text nor a list of token ids")
+            if not ids:
+                raise ValueError(f"input {i} is empty")
+            all_ids.append(ids)
+            if chunking is None:
+                if len(ids) >= eng.max_model_len:
+                    raise ValueError(f"input {i}: {len(ids)} tokens do not fit max_model_len {eng.max_model_len} "
+                                     "(send `chunking` to embed it in windows)")
+                spans_of.append(None)
+                jobs.append((i, ids, 0, None))
+            else:
+                wins = span_windows(len(ids), c, o, eng.max_model_len - 1, int(eng.L["span_slots"]))
+                spans_of.append([sp for _, _, w in wins for sp in w])
+                jobs += [(i, ids[s:e], s, [(a - s, b - s) for a, b in w]) for s, e, w in wins]
+        loop = asyncio.get_running_loop()
+        futs, rids = [], []
+        try:
+            for _, ids, _, spans in jobs:
+                fut = loop.create_future()
+                futs.append(fut)
+                rids.append(eng.submit(
+                    ids, lambda out, fut=fut: loop.call_soon_threadsafe(lambda: fut.done() or fut.set_result(out)),
+                    embed=True, spans=spans, temperature=0.0, max_tokens=1))
+            outs = await asyncio.gather(*futs)
+        except asyncio.CancelledError:
+            for rid in rids:
+                eng.abort(rid)
+            raise
+
+        def unit(v):
+            v = np.asarray(v, dtype=np.float32)
+            n = np.float32(np.linalg.norm(v))
+            return v / n if n > 0 else v
+
+        res = [{"embedding": np.zeros(eng.model_cfg.hidden_size, np.float32), "prompt_tokens": len(ids)}
+               for ids in all_ids]
+        for r, sp in zip(res, spans_of):
+            if sp is not None:
+                r["chunks"] = []
+        for (i, ids, _, spans), out in zip(jobs, outs):
+            if out.embedding is None or (spans and out.span_embeddings is None):
+                raise RuntimeError(f"embedding request did not complete: {out.finish_reason}")
+            res[i]["embedding"] = res[i]["embedding"] + np.float32(len(ids)) * out.embedding
+            for v in (out.span_embeddings if spans else ()):
+                k = len(res[i]["chunks"])
+                a, b = spans_of[i][k]
+                res[i]["chunks"].append({"index": k, "span": [a, b], "text": self.tok.decode(all_ids[i][a:b]),
+                                         "embedding": unit(v)})
+        for r in res:
+            r["embedding"] = unit(r["embedding"])
+        self.usage["calls"] += 1
+        self.usage["prompt_tokens"] += sum(r["prompt_tokens"] for r in res)
+        return res
 
     async def _complete(self, messages, response_format, tools) -> Dict[str, Any]:
         grammar = None

@@ -15,13 +15,14 @@ agents use when each of 64 workers consults memory on every step.
 from __future__ import annotations
 
 import asyncio
+import uuid
 from collections import deque
 from datetime import datetime, timedelta
 from typing import Any, Callable, Deque, Dict, List, Optional, Sequence, Set
 
 from pydantic import BaseModel, ConfigDict, Field
 
-from .embedding import HashingEmbedder
+from .embedding import HashingEmbedder, chunk_spans
 from .semantic_index import SemanticIndex, check_diversity, check_fetch_k
 
 
@@ -111,6 +112,42 @@ class EnhancedMemory:
                 # keeps serving the agents meanwhile
                 return await asyncio.get_running_loop().run_in_executor(None, self._store_items, items, vecs)
             return self._store_items(items, vecs)
+
+    async def store_document(self, text: str, metadata: Optional[Dict[str, Any]] = None,
+                             tags: Optional[Set[str]] = None, priority: int = 0, ttl: Optional[float] = None,
+                             chunk_tokens: int = 256, overlap: int = 32) -> List[int]:
+        """Store a document as one MemoryItem per chunk (chunks of `chunk_tokens` tokens, each
+        starting `overlap` tokens before the end of the one before); returns their rows. An
+        embedder with `embed_document` (EngineEmbedder) embeds all chunks of a context window in
+        one prefill, each chunk vector in the context of the text before it; any other embedder
+        gets the chunk texts -- runs of whitespace-separated words -- one by one. Every item's
+        metadata carries {"document": id, "chunk": i, "span": [a, b]} (token or word ranges)."""
+        if not text:
+            raise ValueError("Text cannot be empty")
+
+        def run() -> List[int]:
+            if hasattr(self.embedder, "embed_document"):
+                texts, vecs, spans = self.embedder.embed_document(text, chunk_tokens=chunk_tokens, overlap=overlap,
+                                                                  return_spans=True)
+            else:
+                words = text.split()
+                spans = chunk_spans(len(words), chunk_tokens, overlap)
+                texts = [" ".join(words[a:b]) for a, b in spans]
+                vecs = None if not texts else self.embedder(texts)
+            keep = [i for i, t in enumerate(texts) if t]  # a chunk that decodes to nothing stores nothing
+            if not keep:
+                return []
+            doc = uuid.uuid4().hex
+            expires = datetime.now() + timedelta(seconds=ttl) if ttl is not None else None
+            items = [MemoryItem(text=texts[i], tags=set(tags or ()), priority=priority, expires_at=expires,
+                                metadata={**(metadata or {}), "document": doc, "chunk": i, "span": list(spans[i])})
+                     for i in keep]
+            return self._store_items(items, vecs[keep])
+
+        async with self._semantic_lock:
+            if getattr(self.index.device, "type", "cpu") == "cuda":
+                return await asyncio.get_running_loop().run_in_executor(None, run)
+            return run()
 
     def _store_items(self, items: List[MemoryItem], vecs=None) -> List[int]:
         if vecs is None:

@@ -475,7 +475,9 @@ class LlamaModel:
         """Returns local-vocab logits [num_logit_rows, V/tp] (bf16).
 
         embed = (rows [>= T] int32, pool [R + 1, d] fp32): every token's final-norm hidden
-        state is added to pool[rows[t]] (embedding requests; row R collects the others)."""
+        state is added to pool[rows[t]] (embedding requests; row R collects the others). A third
+        entry (n_seg [1] int32, segs [4 * cap] int32, span_pool [slots, d] fp32) adds the same
+        rows, segment by segment, into the span accumulators (ops.span_pool)."""
         cfg = self.cfg
         T = num_tokens
         if self.decode_packed and T <= self.DECODE_FUSED_MAX_T:
@@ -567,9 +569,12 @@ class LlamaModel:
     @staticmethod
     def _pool_embed(hn: torch.Tensor, T: int, embed):
         """Sum each token's final-norm hidden state into its pooling row (graph-capturable)."""
-        rows, pool = embed
+        rows, pool = embed[:2]
         pool[-1].zero_()  # the row collecting non-embedding tokens holds one step's sums only
         pool.index_add_(0, rows[:T].long(), hn[:T].float())
+        if len(embed) > 2:  # span segments: ordered sums of the very rows pooled above
+            n_seg, segs, span_pool = embed[2][:3]  # embed[2][3]: the step runs ordered (_forward_mid)
+            ops.kernels.span_pool(hn[:T], n_seg, segs, span_pool)
 
     def _mid_cfg(self, kind: str, T: int) -> dict:
         for mmax, fm, fn, S in self.MID_CFG[kind]:
@@ -641,17 +646,28 @@ class LlamaModel:
                     return path, cfg
         return "mid", self._mid_cfg(kind, T)
 
-    def _gemm(self, kind: str, T: int, x, wp, epi: str, **kw):
+    def _gemm(self, kind: str, T: int, x, wp, epi: str, ordered: bool = False, **kw):
+        """`ordered`: the result must be the same bits from run to run. The prefill kernel's
+        split-K tiles are finished by whichever slice arrives last, which adds the other slices
+        to its own registers, so the order of the adds follows the arrival: such a launch runs
+        every tile over the whole K instead (splits = 1). The other two kernels keep their K
+        splits, because their reduce does not depend on who arrives when: gemm_mid.hip's last
+        ticket holder and gemm_stream.hip's group reduce both start from zero and add every
+        slice's slab, their own included, read back from memory in ascending slab index."""
         path, cfg = self._proj_path(kind, T, wp.shape[0] * 16, wp.shape[1] * 32)
+        if ordered and path == "pf":
+            cfg = dict(cfg, splits=1)
         fn = {"pf": ops.prefill_gemm, "stream": ops.stream_gemm}.get(path, ops.mid_gemm)
         return fn(x, wp, epi, **cfg, **kw)
 
-    def _qkv_rope(self, T: int, x, wp, eps, q, k_cache, v_cache, meta, ss_in):
+    def _qkv_rope(self, T: int, x, wp, eps, q, k_cache, v_cache, meta, ss_in, ordered: bool = False):
         H, KVh = self.h_local, self.kv_local
         if T <= min(self.DEC_QKV_MAX_T, 64) and self.device.type == "cuda":
             return ops.decode_qkv_rope(x, wp, eps, q, k_cache, v_cache, meta.positions, meta.slots, self.cos_sin,
                                        H, KVh)
         path, cfg = self._proj_path("qkv", T, wp.shape[0] * 16, wp.shape[1] * 32)
+        if ordered and path == "pf":  # as in _gemm
+            cfg = dict(cfg, splits=1)
         fn = {"pf": ops.prefill_qkv_rope, "stream": ops.stream_qkv_rope}.get(path, ops.mid_qkv_rope)
         return fn(x, wp, eps, q, k_cache, v_cache, meta.positions, meta.slots, self.cos_sin, H, KVh,
                   ss_in=ss_in, **cfg)
@@ -681,11 +697,23 @@ class LlamaModel:
         if not h.is_contiguous():
             h = h.contiguous()
         ss_a, ss_b = self._ss[0, :T], self._ss[1, :T]
+        # a step that pools spans promises the same bits from run to run, and the residual
+        # epilogues add a row's statistics across workgroups with fp32 atomics, in arrival order:
+        # such a step (TP = 1) takes them from row_sumsq behind each residual launch instead
+        # (one wave per row, a fixed order), two small launches more per layer, and runs its
+        # prefill-kernel projections without split-K (_gemm). This costs about 10 % of such a
+        # step and changes the kernel route of every row batched into it; the span sums are
+        # ordered either way, so the caller may switch it off (EngineConfig.embed_span_ordered,
+        # the fourth entry of embed[2]) and take final-norm rows that differ in their last bits
+        # from run to run, as every other step's do. That the bits repeat with it on is
+        # measured on two model shapes (tests/test_span_embeddings_gpu.py), and argued only for
+        # the projections (_gemm) and the row statistics, not proven for the whole step.
+        ordered = embed is not None and len(embed) > 2 and not tp and (len(embed[2]) < 4 or bool(embed[2][3]))
         ops.row_sumsq(h, out=ss_a)
         ss_b.zero_()
         for li, L in enumerate(self.layers):
             q = torch.empty(T, H, hd, dtype=self.dtype, device=self.device)
-            self._qkv_rope(T, h, L["wqkv_p"], eps, q, kv.k[li], kv.v[li], meta, ss_a)
+            self._qkv_rope(T, h, L["wqkv_p"], eps, q, kv.k[li], kv.v[li], meta, ss_a, ordered)
             attn = torch.empty(T, H, hd, dtype=self.dtype, device=self.device)
             ops.paged_attention(attn, part_o, part_ml, q, kv.k[li], kv.v[li], meta.items, meta.n_items,
                                 meta.att_counters, meta.q_start, meta.q_len, meta.ctx_len,
@@ -695,11 +723,17 @@ class LlamaModel:
             if tp:  # all-reduce + residual + the next norm's row statistics in one launch;
                 # ss_b was zeroed by the previous down all-reduce (or above), ss_a is zeroed here
                 self.tp.all_reduce_add(self._gemm("o", T, a2, L["wo_p"], "plain"), h, ss=ss_b, ss_zero=ss_a)
+            elif ordered:
+                self._gemm("o", T, a2, L["wo_p"], "resid", ordered=True, resid=h, out=h)
+                ops.row_sumsq(h, out=ss_b)
             else:  # ss_b was zeroed by the previous down launch (or above)
                 self._gemm("o", T, a2, L["wo_p"], "resid", resid=h, out=h, ss_out=ss_b, ss_zero=ss_a)
-            a = self._gemm("gate_up", T, h, L["w13_p"], "silu", norm=True, eps=eps, ss_in=ss_b)
+            a = self._gemm("gate_up", T, h, L["w13_p"], "silu", ordered=ordered, norm=True, eps=eps, ss_in=ss_b)
             if tp:
                 self.tp.all_reduce_add(self._gemm("down", T, a, L["w2_p"], "plain"), h, ss=ss_a, ss_zero=ss_b)
+            elif ordered:
+                self._gemm("down", T, a, L["w2_p"], "resid", ordered=True, resid=h, out=h)
+                ops.row_sumsq(h, out=ss_a)
             else:
                 self._gemm("down", T, a, L["w2_p"], "resid", resid=h, out=h, ss_out=ss_a, ss_zero=ss_b)
         if embed is not None:

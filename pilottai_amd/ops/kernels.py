@@ -136,6 +136,21 @@ def kv_copy(k_cache, v_cache, n_copies, copies) -> None:
     ref.kv_copy(k_cache, v_cache, n_copies, copies)
 
 
+def span_pool(hn, n_seg, segs, pool) -> None:
+    """Span pooling (csrc/ops/span_pool.hip): for each of the first `n_seg[0]` (first_row, n_rows,
+    slot, init) quadruples of `segs`, pool[slot] = (0 if init else pool[slot]) + hn[first_row] + ...
+    + hn[first_row + n_rows - 1], the rows added one by one in that order in fp32. `hn` is [T, d]
+    bf16 with d % 8 == 0 (ValueError otherwise), `pool` [slots, d] fp32; the count and the
+    quadruples are int32 tensors on hn's device (graph-capturable: a fixed launch shape). A segment
+    that leaves hn's rows or pool's slots is skipped."""
+    if hn.shape[-1] % 8 != 0:
+        raise ValueError(f"span_pool: the row length {hn.shape[-1]} must be a multiple of 8")
+    if _on_gpu(hn):
+        require_native().span_pool(hn, n_seg, segs, pool)
+        return
+    ref.span_pool(hn, n_seg, segs, pool)
+
+
 def paged_attention(out, part_o, part_ml, q, k_cache, v_cache, items, n_items, counters,
                     q_start, q_len, ctx_len, block_table, scale: float, num_seqs: Optional[int] = None,
                     part_size: Optional[torch.Tensor] = None, waves: int = 4):

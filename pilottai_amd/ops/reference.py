@@ -113,6 +113,28 @@ def kv_copy(k_cache, v_cache, n_copies, copies):
         v_cache[:, dst, :, :, :j] = v_cache[:, src, :, :, :j]
 
 
+def span_pool(hn, n_seg, segs, pool):
+    """hn [T, d] bf16, pool [slots, d] fp32 (updated in place): for each of the first n_seg[0]
+    (first_row, n_rows, slot, init) quadruples, the rows are added to the slot's accumulator one by
+    one in ascending order, each a round-to-nearest fp32 add of the exactly converted bf16 value,
+    starting from +0 (init) or from the accumulator. Segments out of bounds are skipped."""
+    x = hn.detach().cpu().float().numpy()
+    acc_all = pool.detach().cpu().numpy() if isinstance(pool, torch.Tensor) else pool
+    T, slots = x.shape[0], acc_all.shape[0]
+    words = segs.detach().cpu().reshape(-1) if isinstance(segs, torch.Tensor) else np.asarray(segs).reshape(-1)
+    n = min(int(n_seg.reshape(-1)[0]), len(words) // 4)
+    for first, rows, slot, init in np.asarray(words[: 4 * max(0, n)]).reshape(-1, 4).tolist():
+        if rows <= 0 or first < 0 or first + rows > T or not 0 <= slot < slots:
+            continue
+        acc = np.zeros(x.shape[1], np.float32) if init else acc_all[slot].astype(np.float32, copy=True)
+        for r in range(first, first + rows):
+            acc = acc + x[r]
+        acc_all[slot] = acc
+    if isinstance(pool, torch.Tensor) and pool.device.type != "cpu":
+        pool.copy_(torch.from_numpy(acc_all))
+    return pool
+
+
 def paged_attention(q, k_cache, v_cache, q_start, q_len, ctx_len, block_table, scale):
     """q [T, H, 128]; returns out [T, H, 128] (fp32 math, causal within context)."""
     T, H, hd = q.shape

@@ -15,6 +15,18 @@ speak:
                                log-probability of each candidate as the continuation of the context
                                (nothing is generated; the candidates share the context's KV). -inf is
                                sent as -9999.0; malformed bodies and the model-free backend answer 400
+    POST /v1/embeddings        OpenAI's shape: {"input": text | [text, ...] | [token id, ...] | [[token id, ...], ...],
+                               "model", "encoding_format": "float" | "base64" (little-endian fp32)} ->
+                               {"object": "list", "data": [{"object": "embedding", "index", "embedding"}], "model",
+                               "usage": {"prompt_tokens", "total_tokens"}}: the L2-normalised mean final-norm
+                               hidden state of each input, `hidden_size` entries (`dimensions` may only name that
+                               size). Extension "chunking": {"chunk_tokens": n, "overlap": m} adds to each item
+                               "chunks": [{"index", "span": [a, b], "text", "embedding"}] -- the vectors of
+                               overlapping token chunks, each computed inside the document in the same prefill
+                               (the engine's span requests) -- and lifts the context limit: a longer input is
+                               embedded in windows of whole chunks. Empty input, ids outside the vocabulary, an
+                               input of max_model_len tokens or more without chunking, a malformed chunking object
+                               and the model-free backend answer 400
 
 `response_format` accepts the OpenAI forms and one extension:
 * {"type": "json_schema", "json_schema": {"name": ..., "schema": {...}}}: a JSON Schema
@@ -255,6 +267,41 @@ def _prediction(body: Dict[str, Any]) -> Dict[str, Any]:
     return out
 
 
+def _embedding_inputs(inp: Any) -> List[Any]:
+    """The `input` of /v1/embeddings as a list of texts or token id lists: a string, a list of
+    strings, a list of token ids, or a list of such lists. ValueError -> 400."""
+    is_id = lambda t: isinstance(t, int) and not isinstance(t, bool)  # noqa: E731
+    if isinstance(inp, str):
+        inp = [inp]
+    elif isinstance(inp, list) and inp and all(is_id(t) for t in inp):
+        inp = [inp]
+    if not isinstance(inp, list) or not inp:
+        raise ValueError("input must be a non-empty string, list of strings, list of token ids or list of such lists")
+    if all(isinstance(x, str) for x in inp):
+        if any(not x for x in inp):
+            raise ValueError("input texts must not be empty")
+    elif all(isinstance(x, list) and x and all(is_id(t) for t in x) for x in inp):
+        pass
+    else:
+        raise ValueError("input must hold only non-empty strings or only non-empty lists of token ids")
+    return inp
+
+
+def _chunking(ch: Any) -> Optional[Dict[str, int]]:
+    """The `chunking` extension of /v1/embeddings: {"chunk_tokens": n >= 1, "overlap": 0 <= m < n}
+    (overlap 0 when absent); None when the request has none. ValueError -> 400."""
+    if ch is None:
+        return None
+    if not isinstance(ch, dict) or set(ch) - {"chunk_tokens", "overlap"} or "chunk_tokens" not in ch:
+        raise ValueError('chunking must be an object {"chunk_tokens": n, "overlap": m}')
+    c, o = ch["chunk_tokens"], ch.get("overlap", 0)
+    if isinstance(c, bool) or not isinstance(c, int) or c < 1:
+        raise ValueError("chunking.chunk_tokens must be an integer >= 1")
+    if isinstance(o, bool) or not isinstance(o, int) or not 0 <= o < c:
+        raise ValueError("chunking.overlap must be an integer in [0, chunk_tokens)")
+    return {"chunk_tokens": c, "overlap": o}
+
+
 def _tools(body: Dict[str, Any]) -> Optional[List[Dict[str, Any]]]:
     tools = body.get("tools")
     if not tools:
@@ -415,6 +462,46 @@ def create_app(llm, model_name: Optional[str] = None, engine=None) -> FastAPI:
                 "model": name, "scores": scores,
                 "usage": {"prompt_tokens": pt, "completion_tokens": 0, "total_tokens": pt,
                           "cached_prompt_tokens": int(used.get("cached_prompt_tokens", 0))}}
+
+    @app.post("/v1/embeddings")
+    async def embeddings(body: Dict[str, Any]):
+        import base64
+
+        import numpy as np
+
+        if not getattr(llm, "supports_embeddings", False):
+            raise HTTPException(400, f"the {getattr(llm, 'provider', 'configured')} backend cannot embed text")
+        try:
+            inputs = _embedding_inputs(body.get("input"))
+            fmt = body.get("encoding_format", "float")
+            if fmt not in ("float", "base64"):
+                raise ValueError('encoding_format must be "float" or "base64"')
+            eng = engine or getattr(llm, "engine", None)
+            hidden = getattr(getattr(eng, "model_cfg", None), "hidden_size", None)
+            dims = body.get("dimensions")
+            if dims is not None and (isinstance(dims, bool) or not isinstance(dims, int) or dims != hidden):
+                raise ValueError(f"dimensions must be the model's hidden size {hidden}")
+            chunking = _chunking(body.get("chunking"))
+            res = await llm.embed(inputs, chunking=chunking)
+        except (NotImplementedError, ValueError) as e:
+            raise HTTPException(400, str(e))
+        except Exception as e:  # noqa: BLE001
+            raise HTTPException(500, f"embedding failed: {e}")
+
+        def wire(v):
+            v = np.ascontiguousarray(v, dtype="<f4")
+            return base64.b64encode(v.tobytes()).decode("ascii") if fmt == "base64" else [float(x) for x in v]
+
+        data = []
+        for i, r in enumerate(res):
+            item = {"object": "embedding", "index": i, "embedding": wire(r["embedding"])}
+            if "chunks" in r:
+                item["chunks"] = [{"index": c["index"], "span": list(c["span"]), "text": c["text"],
+                                   "embedding": wire(c["embedding"])} for c in r["chunks"]]
+            data.append(item)
+        pt = sum(int(r.get("prompt_tokens") or 0) for r in res)
+        return {"object": "list", "data": data, "model": body.get("model") or name,
+                "usage": {"prompt_tokens": pt, "total_tokens": pt}}
 
     return app
 
