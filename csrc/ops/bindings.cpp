@@ -81,6 +81,13 @@ int pa_decode_qkv_rope(const void* x, const void* wp, int M, int N, int K, int l
                        void* k_cache, void* v_cache, const int* positions, const int* slots,
                        const float* cos_sin, int H, int KV, int nt, int waves, int splits, float* ws,
                        long long ws_floats, int* counters, int n_counters, hipStream_t st);
+int pa_decode_gemm_fp8(void* y, const void* x, const void* wp8, const float* scale, const void* resid, int M, int N,
+                       int K, int ldx, int ldy, int ldr, int epi, int norm, float eps, int nt, int waves,
+                       int splits, float* ws, long long ws_floats, int* counters, int n_counters, hipStream_t st);
+int pa_decode_qkv_rope_fp8(const void* x, const void* wp8, const float* scale, int M, int N, int K, int ldx,
+                           float eps, void* q_out, void* k_cache, void* v_cache, const int* positions,
+                           const int* slots, const float* cos_sin, int H, int KV, int nt, int waves, int splits,
+                           float* ws, long long ws_floats, int* counters, int n_counters, hipStream_t st);
 int pa_mid_gemm_plan(int M, int N, int K, int epi, int* fm, int* fn, int* S);
 long long pa_mid_gemm_ws_floats(int M, int N, int K, int fm, int fn, int S);
 int pa_mid_gemm(void* y, const void* x, const void* wp, const void* resid, float* ws, long long ws_floats,
@@ -327,16 +334,28 @@ bool skinny_gemm(at::Tensor y, at::Tensor x, at::Tensor w) {
 // y = epi(rownorm(x) . W^T) on fragment-major packed weights wp [N/16, K/32, 64, 8]
 // (csrc/ops/gemm_decode.hip). epi 0 plain, 1 silu(gate)*up (y has N/2 columns),
 // 2 y = resid + acc. Returns false if the shape is not handled.
-bool decode_gemm(at::Tensor y, at::Tensor x, at::Tensor wp, c10::optional<at::Tensor> resid, int64_t epi,
-                 bool norm, double eps, int64_t nt, int64_t waves, int64_t splits, c10::optional<at::Tensor> ws,
-                 c10::optional<at::Tensor> counters) {
+// With `scale` ([N] fp32, packed column order) wp holds e4m3 bytes in the same index layout
+// (csrc/ops/gemm_decode_fp8.hip).
+const float* fp8_scale(const at::Tensor& scale, int N) {
+  check_gpu(scale, "scale");
+  check_dtype(scale, at::kFloat, "scale");
+  TORCH_CHECK(scale.dim() == 1 && scale.size(0) == N && scale.is_contiguous(), "scale must be contiguous [N = ", N, "]");
+  return scale.data_ptr<float>();
+}
+
+bool decode_gemm_impl(at::Tensor y, at::Tensor x, at::Tensor wp, const at::Tensor* scale,
+                      c10::optional<at::Tensor> resid, int64_t epi, bool norm, double eps, int64_t nt,
+                      int64_t waves, int64_t splits, c10::optional<at::Tensor> ws,
+                      c10::optional<at::Tensor> counters) {
   check_gpu(wp, "wp");
   TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.stride(1) == 1, "x must be a 2-D GPU tensor, unit inner stride");
   TORCH_CHECK(y.is_cuda() && y.dim() == 2 && y.stride(1) == 1, "y must be a 2-D GPU tensor, unit inner stride");
-  check_dtype(x, at::kBFloat16, "x"); check_dtype(wp, at::kBFloat16, "wp"); check_dtype(y, at::kBFloat16, "y");
+  check_dtype(x, at::kBFloat16, "x"); check_dtype(y, at::kBFloat16, "y");
+  check_dtype(wp, scale ? at::kFloat8_e4m3fn : at::kBFloat16, "wp");
   TORCH_CHECK(wp.dim() == 4 && wp.size(2) == 64 && wp.size(3) == 8, "wp must be packed [N/16, K/32, 64, 8]");
   const int M = x.size(0), K = x.size(1), N = wp.size(0) * 16;
   TORCH_CHECK(wp.size(1) * 32 == K, "packed weight K ", wp.size(1) * 32, " != x K ", K);
+  const float* sp = scale ? fp8_scale(*scale, N) : nullptr;
   TORCH_CHECK(x.stride(0) % 8 == 0 && K % 8 == 0, "x rows must be 16-byte aligned");
   const int NO = epi == 1 ? N / 2 : N;
   TORCH_CHECK(y.size(0) == M && y.size(1) == NO, "y shape [", y.size(0), ", ", y.size(1), "] != [", M, ", ", NO, "]");
@@ -360,27 +379,46 @@ bool decode_gemm(at::Tensor y, at::Tensor x, at::Tensor wp, c10::optional<at::Te
     check_dtype(*ws, at::kFloat, "ws"); check_dtype(*counters, at::kInt, "counters");
     wsp = ws->data_ptr<float>(); wsn = ws->numel(); cp = counters->data_ptr<int>(); cn = counters->numel();
   }
-  const int rc = pa_decode_gemm(y.data_ptr(), x.data_ptr(), wp.data_ptr(), rp, M, N, K, x.stride(0), y.stride(0),
-                                ldr, (int)epi, norm ? 1 : 0, (float)eps, (int)nt, (int)waves, (int)splits, wsp, wsn,
-                                cp, cn, cur_stream());
+  const int rc =
+      scale ? pa_decode_gemm_fp8(y.data_ptr(), x.data_ptr(), wp.data_ptr(), sp, rp, M, N, K, x.stride(0),
+                                 y.stride(0), ldr, (int)epi, norm ? 1 : 0, (float)eps, (int)nt, (int)waves,
+                                 (int)splits, wsp, wsn, cp, cn, cur_stream())
+            : pa_decode_gemm(y.data_ptr(), x.data_ptr(), wp.data_ptr(), rp, M, N, K, x.stride(0), y.stride(0),
+                             ldr, (int)epi, norm ? 1 : 0, (float)eps, (int)nt, (int)waves, (int)splits, wsp, wsn,
+                             cp, cn, cur_stream());
   TORCH_CHECK(rc >= 0, "decode_gemm launch failed");
   return rc == 0;
 }
 
+bool decode_gemm(at::Tensor y, at::Tensor x, at::Tensor wp, c10::optional<at::Tensor> resid, int64_t epi,
+                 bool norm, double eps, int64_t nt, int64_t waves, int64_t splits, c10::optional<at::Tensor> ws,
+                 c10::optional<at::Tensor> counters) {
+  return decode_gemm_impl(y, x, wp, nullptr, resid, epi, norm, eps, nt, waves, splits, ws, counters);
+}
+
+bool decode_gemm_fp8(at::Tensor y, at::Tensor x, at::Tensor wp8, at::Tensor scale, c10::optional<at::Tensor> resid,
+                     int64_t epi, bool norm, double eps, int64_t nt, int64_t waves, int64_t splits,
+                     c10::optional<at::Tensor> ws, c10::optional<at::Tensor> counters) {
+  return decode_gemm_impl(y, x, wp8, &scale, resid, epi, norm, eps, nt, waves, splits, ws, counters);
+}
+
 // Decode QKV projection + RoPE + paged KV write (csrc/ops/gemm_decode.hip, EPI_ROPE).
-void decode_qkv_rope(at::Tensor x, at::Tensor wp, double eps, at::Tensor q_out, at::Tensor k_cache,
-                     at::Tensor v_cache, at::Tensor positions, at::Tensor slots, at::Tensor cos_sin, int64_t H,
-                     int64_t KV, int64_t splits, c10::optional<at::Tensor> ws, c10::optional<at::Tensor> counters) {
+void decode_qkv_rope_impl(at::Tensor x, at::Tensor wp, const at::Tensor* scale, double eps, at::Tensor q_out,
+                          at::Tensor k_cache, at::Tensor v_cache, at::Tensor positions, at::Tensor slots,
+                          at::Tensor cos_sin, int64_t H, int64_t KV, int64_t splits, c10::optional<at::Tensor> ws,
+                          c10::optional<at::Tensor> counters) {
   check_gpu(wp, "wp"); check_gpu(q_out, "q_out"); check_gpu(k_cache, "k_cache"); check_gpu(v_cache, "v_cache");
   check_gpu(positions, "positions"); check_gpu(slots, "slots"); check_gpu(cos_sin, "cos_sin");
   TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.stride(1) == 1, "x must be a 2-D GPU tensor, unit inner stride");
-  check_dtype(x, at::kBFloat16, "x"); check_dtype(wp, at::kBFloat16, "wp"); check_dtype(q_out, at::kBFloat16, "q_out");
+  check_dtype(x, at::kBFloat16, "x"); check_dtype(q_out, at::kBFloat16, "q_out");
+  check_dtype(wp, scale ? at::kFloat8_e4m3fn : at::kBFloat16, "wp");
   check_dtype(k_cache, at::kBFloat16, "k_cache"); check_dtype(v_cache, at::kBFloat16, "v_cache");
   check_dtype(positions, at::kInt, "positions"); check_dtype(slots, at::kInt, "slots");
   check_dtype(cos_sin, at::kFloat, "cos_sin");
   TORCH_CHECK(wp.dim() == 4 && wp.size(2) == 64 && wp.size(3) == 8, "wp must be packed [N/16, K/32, 64, 8]");
   const int M = x.size(0), K = x.size(1), N = wp.size(0) * 16;
   TORCH_CHECK(wp.size(1) * 32 == K, "packed weight K mismatch");
+  const float* sp = scale ? fp8_scale(*scale, N) : nullptr;
   TORCH_CHECK(N == (H + 2 * KV) * 128, "packed QKV has ", N, " columns, expected (H + 2 KV) * 128");
   TORCH_CHECK(q_out.numel() >= (int64_t)M * H * 128, "q_out too small");
   TORCH_CHECK(positions.numel() >= M && slots.numel() >= M, "positions/slots shorter than x");
@@ -398,11 +436,31 @@ void decode_qkv_rope(at::Tensor x, at::Tensor wp, double eps, at::Tensor q_out, 
     check_dtype(*ws, at::kFloat, "ws"); check_dtype(*counters, at::kInt, "counters");
     wsp = ws->data_ptr<float>(); wsn = ws->numel(); cp = counters->data_ptr<int>(); cn = counters->numel();
   }
-  const int rc = pa_decode_qkv_rope(x.data_ptr(), wp.data_ptr(), M, N, K, x.stride(0), (float)eps, q_out.data_ptr(),
-                                    k_cache.data_ptr(), v_cache.data_ptr(), positions.data_ptr<int>(),
-                                    slots.data_ptr<int>(), cos_sin.data_ptr<float>(), (int)H, (int)KV, 0, 0,
-                                    (int)splits, wsp, wsn, cp, cn, cur_stream());
+  const int rc =
+      scale ? pa_decode_qkv_rope_fp8(x.data_ptr(), wp.data_ptr(), sp, M, N, K, x.stride(0), (float)eps,
+                                     q_out.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                                     positions.data_ptr<int>(), slots.data_ptr<int>(), cos_sin.data_ptr<float>(),
+                                     (int)H, (int)KV, 0, 0, (int)splits, wsp, wsn, cp, cn, cur_stream())
+            : pa_decode_qkv_rope(x.data_ptr(), wp.data_ptr(), M, N, K, x.stride(0), (float)eps, q_out.data_ptr(),
+                                 k_cache.data_ptr(), v_cache.data_ptr(), positions.data_ptr<int>(),
+                                 slots.data_ptr<int>(), cos_sin.data_ptr<float>(), (int)H, (int)KV, 0, 0,
+                                 (int)splits, wsp, wsn, cp, cn, cur_stream());
   check_rc(rc < 0 ? rc : (rc > 0 ? -1 : 0), "decode_qkv_rope");
+}
+
+void decode_qkv_rope(at::Tensor x, at::Tensor wp, double eps, at::Tensor q_out, at::Tensor k_cache,
+                     at::Tensor v_cache, at::Tensor positions, at::Tensor slots, at::Tensor cos_sin, int64_t H,
+                     int64_t KV, int64_t splits, c10::optional<at::Tensor> ws, c10::optional<at::Tensor> counters) {
+  decode_qkv_rope_impl(x, wp, nullptr, eps, q_out, k_cache, v_cache, positions, slots, cos_sin, H, KV, splits, ws,
+                       counters);
+}
+
+void decode_qkv_rope_fp8(at::Tensor x, at::Tensor wp8, at::Tensor scale, double eps, at::Tensor q_out,
+                         at::Tensor k_cache, at::Tensor v_cache, at::Tensor positions, at::Tensor slots,
+                         at::Tensor cos_sin, int64_t H, int64_t KV, int64_t splits, c10::optional<at::Tensor> ws,
+                         c10::optional<at::Tensor> counters) {
+  decode_qkv_rope_impl(x, wp8, &scale, eps, q_out, k_cache, v_cache, positions, slots, cos_sin, H, KV, splits, ws,
+                       counters);
 }
 
 const float* opt_rows(const c10::optional<at::Tensor>& t, int M, const char* name) {
@@ -1459,6 +1517,14 @@ PYBIND11_MODULE(_C, m) {
   m.def("decode_qkv_rope", &decode_qkv_rope, py::arg("x"), py::arg("wp"), py::arg("eps"), py::arg("q_out"),
         py::arg("k_cache"), py::arg("v_cache"), py::arg("positions"), py::arg("slots"), py::arg("cos_sin"),
         py::arg("H"), py::arg("KV"), py::arg("splits") = 0, py::arg("ws") = py::none(),
+        py::arg("counters") = py::none());
+  m.def("decode_gemm_fp8", &decode_gemm_fp8, py::arg("y"), py::arg("x"), py::arg("wp8"), py::arg("scale"),
+        py::arg("resid") = py::none(), py::arg("epi") = 0, py::arg("norm") = false, py::arg("eps") = 1e-5,
+        py::arg("nt") = 0, py::arg("waves") = 0, py::arg("splits") = 0, py::arg("ws") = py::none(),
+        py::arg("counters") = py::none());
+  m.def("decode_qkv_rope_fp8", &decode_qkv_rope_fp8, py::arg("x"), py::arg("wp8"), py::arg("scale"), py::arg("eps"),
+        py::arg("q_out"), py::arg("k_cache"), py::arg("v_cache"), py::arg("positions"), py::arg("slots"),
+        py::arg("cos_sin"), py::arg("H"), py::arg("KV"), py::arg("splits") = 0, py::arg("ws") = py::none(),
         py::arg("counters") = py::none());
   m.def("mid_gemm", &mid_gemm, py::arg("y"), py::arg("x"), py::arg("wp"), py::arg("resid"), py::arg("ws"),
         py::arg("counters"), py::arg("epi") = 0, py::arg("ss_in") = py::none(), py::arg("ss_out") = py::none(),

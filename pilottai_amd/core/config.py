@@ -91,6 +91,9 @@ class LLMConfig(BaseModel):
     # prompt-lookup drafts, the request default (off): decode steps propose the continuation of the
     # last tokens' latest earlier occurrence in the prompt or the reply and verify it at once
     prompt_lookup: bool = False
+    # provider "local": weight quantisation of the engine this model is served by (None, "fp8":
+    # EngineConfig.weight_quant); the model-free and HTTP backends ignore it
+    weight_quant: Optional[str] = None
     max_tokens: int = Field(default=2000, gt=0)
     function_calling_model: Optional[str] = None
     system_template: Optional[str] = None

@@ -119,6 +119,11 @@ class EngineConfig:
     # keep the row-major projection weights beside the packed ones (None: only when some step can
     # leave the packed-weight path, i.e. prefill_max_t / mid_max_t below max_num_batched_tokens)
     keep_dense: Optional[bool] = None
+    # "fp8": the layer projections quantised per output channel to e4m3 with power-of-two scales,
+    # one weight set on every kernel route (models/llama.py); fp8_decode: decode-sized steps
+    # stream the FP8 packed copy (half the bytes, same bits) instead of the bf16 one
+    weight_quant: Optional[str] = None
+    fp8_decode: bool = True
     # projections ("qkv", "o", "gate_up", "down") whose PF_CFG prefill-kernel rows also apply to
     # <= 256-token steps (None: model default)
     pf_midrange: Optional[List[str]] = None
@@ -292,7 +297,8 @@ class LLMEngine:
                       LlamaModel.PREFILL_MAX_T if cfg.prefill_max_t is None else int(cfg.prefill_max_t))
             keep_dense = True if lim < cfg.max_num_batched_tokens else None
         self.model = LlamaModel(mc, self.device, tp=self.tp, seed=cfg.seed, weights_path=cfg.weights_path,
-                                decode_pack=cfg.decode_fused, keep_dense=keep_dense)
+                                decode_pack=cfg.decode_fused, keep_dense=keep_dense,
+                                weight_quant=cfg.weight_quant, fp8_decode=cfg.fp8_decode)
         if cfg.decode_fused_max_t is not None:
             self.model.DECODE_FUSED_MAX_T = int(cfg.decode_fused_max_t)
         if cfg.mid_max_t is not None:
@@ -1814,6 +1820,7 @@ class LLMEngine:
             "spec_draft_steps": s.spec_draft_steps, "spec_runs_full": s.spec_runs_full,
             "kv_cache_gb": self.kv.k.numel() * 2 * 2 / 2**30,
             "weights_gb": self.model.weight_bytes() / 2**30,
+            "weight_quant": self.model.weight_quant, "fp8_decode": self.model.fp8_decode,
         })
         if self.on_gpu:
             st["hbm_used_gb"] = torch.cuda.memory_allocated(self.device) / 2**30

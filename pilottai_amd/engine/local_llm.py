@@ -253,7 +253,8 @@ class LocalLLM(BaseLLM):
         if engine is None:
             from .registry import get_engine
 
-            engine = get_engine(self.model_name)
+            wq = _cfg_get(config, "weight_quant", None)
+            engine = get_engine(self.model_name, **({"weight_quant": wq} if wq is not None else {}))
         self.engine = engine
         # node-wide shared context (Serve.broadcast_context): a leading system
         # message whose KV every GPU pre-warmed into its prefix cache

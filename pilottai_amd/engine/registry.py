@@ -25,6 +25,11 @@ def get_engine(model: str = "llama-3-8b", **overrides) -> LLMEngine:
     key = model.lower()
     with _LOCK:
         eng = _ENGINES.get(key)
+        if eng is not None and "weight_quant" in overrides:
+            have = getattr(eng.model, "weight_quant", None)
+            if have != overrides["weight_quant"]:
+                raise ValueError(f"this process already holds an engine for {key!r} with weight_quant={have!r} "
+                                 f"(asked for {overrides['weight_quant']!r}): one engine per model per process")
         if eng is None:
             kw = dict(_DEFAULTS.get(key, {}))
             kw.update(overrides)

@@ -244,8 +244,16 @@ class LlamaModel:
 
     def __init__(self, cfg: LlamaConfig, device, dtype=torch.bfloat16, tp: Optional[TPGroup] = None,
                  seed: int = 0, weights_path: Optional[str] = None, decode_pack: Optional[bool] = None,
-                 keep_dense: Optional[bool] = None):
-        """keep_dense: keep the row-major projection weights after packing (None: only on CPU,
+                 keep_dense: Optional[bool] = None, weight_quant: Optional[str] = None, fp8_decode: bool = True):
+        """weight_quant="fp8": the four layer projections are quantised per output channel to
+        OCP e4m3 with power-of-two scales (ops.quantize_fp8_rows, RMSNorm weights folded first).
+        q * scale is exact in bf16, so the bf16 packed copy is rebuilt from it and EVERY route
+        (decode, mid, stream, prefill, dense) computes with the same weights; fp8_decode adds the
+        FP8 packed copy that decode-sized steps stream instead (half the bytes, bit-identical
+        results: csrc/ops/gemm_decode_fp8.hip). fp8_decode=False is the same quantised model on
+        the bf16 decode kernels. Embedding, final norm and LM head stay bf16.
+
+        keep_dense: keep the row-major projection weights after packing (None: only on CPU,
         where the tests read them). On the GPU the packed copy is the ONLY copy (VERDICT r5
         item 6: the row-major one was 15 GB of dead HBM on 8B and kept 70B at TP=1 off the hand
         kernels); the dense reference paths unpack a layer at a time on demand."""
@@ -253,6 +261,16 @@ class LlamaModel:
         self.device = torch.device(device)
         self.dtype = dtype
         self.tp = tp or TPGroup.single()
+        if weight_quant not in (None, "fp8"):
+            raise ValueError(f"unknown weight_quant {weight_quant!r} (None or 'fp8')")
+        if weight_quant and self.tp.size > 1:
+            raise ValueError("weight_quant='fp8' needs tensor-parallel size 1: per-channel scales of "
+                             "row-parallel shards are not designed yet")
+        if weight_quant and decode_pack is False:
+            raise ValueError("weight_quant='fp8' lives on the packed weight copies: it cannot be combined "
+                             "with decode_pack=False (EngineConfig.decode_fused=False)")
+        self.weight_quant = weight_quant
+        self.fp8_decode = bool(fp8_decode) and weight_quant == "fp8"
         # routing-table overrides for in-engine A/Bs (tools/midrange_ab.py style): a JSON object
         # {"STREAM_CFG": {"qkv": [[64, [1, 1, 6, 1, 4, 4]]]}, "MID_CFG": {...}, "PF_CFG": {...},
         #  "PF_MIDRANGE": ["gate_up", "qkv"]} whose per-projection rows replace the class table's
@@ -292,6 +310,8 @@ class LlamaModel:
         self.keep_dense = (self.device.type != "cuda") if keep_dense is None else bool(keep_dense)
         if decode_pack is None:
             decode_pack = self._pack_fits()
+        if weight_quant:
+            self._check_quant_fits(decode_pack)
         if decode_pack:
             self._pack_decode_weights()
 
@@ -304,19 +324,47 @@ class LlamaModel:
         if self.device.type != "cuda":
             return True
         total = torch.cuda.get_device_properties(self.device).total_memory
+        extra = self._fp8_copy_bytes() if self.fp8_decode else 0  # + the FP8 decode copies
         if self.keep_dense:
-            return 2 * self.weight_bytes() <= 0.45 * total
-        return self.weight_bytes() <= 0.7 * total
+            return 2 * self.weight_bytes() + extra <= 0.45 * total
+        return self.weight_bytes() + extra <= 0.7 * total
+
+    def _fp8_copy_bytes(self) -> int:
+        """Bytes of the FP8 packed copies + fp32 scales of every layer (Llama-3-8B: 6.98 GB
+        beside 13.96 GB of bf16 layer weights; 70B at TP = 1: 68.5 GB beside 141 GB)."""
+        n = 0
+        for L in self.layers:
+            for k in DENSE_KINDS:
+                w = L[k]
+                n += w.numel() + 4 * w.shape[0]
+        return n
+
+    def _check_quant_fits(self, decode_pack: bool):
+        """weight_quant never falls back to the unquantised model or to another kernel: when the
+        packed copies do not fit beside the KV cache it raises, naming the sizes."""
+        if decode_pack or self.device.type != "cuda":
+            return
+        total = torch.cuda.get_device_properties(self.device).total_memory
+        base, extra = self.weight_bytes(), (self._fp8_copy_bytes() if self.fp8_decode else 0)
+        hint = (": build the model with fp8_decode=False (the same quantised model on the bf16 decode kernels)"
+                if self.fp8_decode else "")
+        raise ValueError(f"weight_quant={self.weight_quant!r}: {base / 1e9:.2f} GB of bf16 weights"
+                         f"{' (kept row-major copy doubles them)' if self.keep_dense else ''} + "
+                         f"{extra / 1e9:.2f} GB of FP8 decode copies do not fit beside the KV cache on a "
+                         f"{total / 1e9:.0f} GB device{hint}")
 
     def _pack_decode_weights(self):
         """Fragment-major copies for ops.decode_gemm, with the RMSNorm weights
         folded into the columns of the matrices they feed (QKV <- ln1, gate_up <-
         ln2), so the decode path needs no separate norm kernel."""
         for L in self.layers:
-            L["wqkv_p"] = ops.pack_decode_qkv_rope(L["wqkv"] * L["ln1"][None, :])
-            L["wo_p"] = ops.pack_decode_weight(L["wo"])
-            L["w13_p"] = ops.pack_decode_gate_up(L["w13"] * L["ln2"][None, :])
-            L["w2_p"] = ops.pack_decode_weight(L["w2"])
+            if self.weight_quant == "fp8":
+                self._pack_layer_fp8(L)
+            else:
+                L["wqkv_p"] = ops.pack_decode_qkv_rope(L["wqkv"] * L["ln1"][None, :])
+                L["wo_p"] = ops.pack_decode_weight(L["wo"])
+                L["w13_p"] = ops.pack_decode_gate_up(L["w13"] * L["ln2"][None, :])
+                L["w2_p"] = ops.pack_decode_weight(L["w2"])
             if not self.keep_dense:  # the packed copy is the only one (freed layer by layer)
                 for k in DENSE_KINDS:
                     del L[k]
@@ -334,6 +382,26 @@ class LlamaModel:
         # RMSNorm row statistics handed from each residual epilogue to the next projection
         self._ss = torch.zeros(2, 1 << 15, dtype=torch.float32, device=self.device)
         self.decode_packed = True
+
+    def _pack_layer_fp8(self, L: Dict[str, torch.Tensor]):
+        """Quantise one layer's projections (norm weights folded first); the bf16 packed copy
+        holds q * scale exactly, the FP8 packed copy + packed-order scales feed the decode
+        kernel. A kept row-major copy is replaced by the dequantised weights too."""
+        plan = (("wqkv", "ln1", ops.pack_decode_qkv_rope, ops.pack_decode_qkv_rope_fp8),
+                ("wo", None, ops.pack_decode_weight, ops.pack_decode_weight_fp8),
+                ("w13", "ln2", ops.pack_decode_gate_up, ops.pack_decode_gate_up_fp8),
+                ("w2", None, ops.pack_decode_weight, ops.pack_decode_weight_fp8))
+        for kind, ln, pack, pack8 in plan:
+            w = L[kind] * L[ln][None, :] if ln else L[kind]
+            q, s = ops.quantize_fp8_rows(w)
+            deq = ops.dequantize_fp8_rows(q, s, self.dtype)
+            del w
+            L[kind + "_p"] = pack(deq)
+            if self.fp8_decode:
+                L[kind + "_p8"], L[kind + "_s8"] = pack8((q, s))
+            if self.keep_dense:
+                L[kind] = (deq.float() / L[ln].float()[None, :]).to(self.dtype) if ln else deq
+            del q, s, deq
 
     def dense(self, L: Dict[str, torch.Tensor], kind: str) -> torch.Tensor:
         """Row-major [N, K] weight `kind` ("wqkv", "wo", "w13", "w2") of layer dict L: the kept
@@ -456,9 +524,10 @@ class LlamaModel:
             n += self.lm_head.numel()
         if getattr(self, "lm_head_p", None) is not None:
             n += self.lm_head_p.numel()
-        for L in self.layers:
-            n += sum(t.numel() for t in L.values())
-        return n * self.embed.element_size()
+        n *= self.embed.element_size()
+        for L in self.layers:  # (the FP8 copies are 1-byte elements, their scales fp32)
+            n += sum(t.numel() * t.element_size() for t in L.values())
+        return n
 
     # -- forward -----------------------------------------------------------------
     def _embed(self, ids: torch.Tensor) -> torch.Tensor:
@@ -534,14 +603,24 @@ class LlamaModel:
             h = h.contiguous()
         for li, L in enumerate(self.layers):
             q = torch.empty(T, H, hd, dtype=self.dtype, device=self.device)
-            ops.decode_qkv_rope(h, L["wqkv_p"], eps, q, kv.k[li], kv.v[li], meta.positions, meta.slots,
-                                self.cos_sin, H, KVh)
+            f8 = "wqkv_p8" in L  # the layer holds the FP8 decode copy (weight_quant + fp8_decode; TP = 1)
+            if f8:
+                ops.decode_qkv_rope_fp8(h, L["wqkv_p8"], L["wqkv_s8"], eps, q, kv.k[li], kv.v[li], meta.positions,
+                                        meta.slots, self.cos_sin, H, KVh)
+            else:
+                ops.decode_qkv_rope(h, L["wqkv_p"], eps, q, kv.k[li], kv.v[li], meta.positions, meta.slots,
+                                    self.cos_sin, H, KVh)
             attn = torch.empty(T, H, hd, dtype=self.dtype, device=self.device)
             ops.paged_attention(attn, part_o, part_ml, q, kv.k[li], kv.v[li], meta.items, meta.n_items,
                                 meta.att_counters, meta.q_start, meta.q_len, meta.ctx_len,
                                 meta.block_table, self.scale, num_seqs=meta.num_seqs, part_size=meta.part_size,
                                 waves=self.ATT_DECODE_WAVES)
             a2 = attn.view(T, H * hd)
+            if f8:
+                ops.decode_gemm_fp8(a2, L["wo_p8"], L["wo_s8"], "resid", resid=h, out=h)
+                a = ops.decode_gemm_fp8(h, L["w13_p8"], L["w13_s8"], "silu", norm=True, eps=eps)
+                ops.decode_gemm_fp8(a, L["w2_p8"], L["w2_s8"], "resid", resid=h, out=h, **self._down_cfg(T))
+                continue
             if tp:  # all-reduce + residual add in one launch (custom_ar.hip RES epilogue)
                 self.tp.all_reduce_add(ops.decode_gemm(a2, L["wo_p"], "plain"), h)
             else:

@@ -830,6 +830,112 @@ def decode_qkv_rope(x: torch.Tensor, wp: torch.Tensor, eps: float, q_out: torch.
     return q_out
 
 
+# ---------------------------------------------------------------------------
+# FP8 (e4m3) copies of the packed decode weights (csrc/ops/gemm_decode_fp8.hip).
+# Per output channel a power-of-two scale (reference.quantize_fp8_rows), so q * scale is exact
+# in bf16 and the FP8 kernel equals the bf16 kernel on the dequantised weights bit for bit.
+# The packed tensors keep the index layout of the bf16 packers with 1-byte elements; the
+# scales travel in PACKED column order (the order in which the kernel's tiles hold columns).
+
+quantize_fp8_rows = ref.quantize_fp8_rows
+dequantize_fp8_rows = ref.dequantize_fp8_rows
+_F8 = torch.float8_e4m3fn
+
+
+def _quantized(w):
+    """(q, scale) from a weight matrix, or a (q, scale) pair passed through."""
+    if isinstance(w, (tuple, list)):
+        q, s = w
+        if q.dtype != _F8:
+            raise ValueError(f"quantised weights must be float8_e4m3fn, got {q.dtype}")
+        return q, s.float()
+    return quantize_fp8_rows(w)
+
+
+def _u8(f, q, *a):
+    # layout ops run on the bytes: not every indexing op exists for float8 tensors
+    return f(q.view(torch.uint8), *a).view(_F8)
+
+
+def pack_decode_weight_fp8(w):
+    """[N, K] (or a quantised (q, scale) pair) -> (wp8 [N/16, K/32, 64, 8] e4m3, scale_p [N])."""
+    q, s = _quantized(w)
+    return _u8(pack_decode_weight, q), s.contiguous()
+
+
+def pack_decode_gate_up_fp8(w13):
+    """[gate; up] -> (wp8 with gate/up tiles interleaved, scale_p interleaved the same way)."""
+    q, s = _quantized(w13)
+    F2 = q.shape[0]
+    if F2 % 32:
+        raise ValueError(f"cannot pack a [{F2}, {q.shape[1]}] gate_up weight (needs 2F % 32 == 0)")
+    return _u8(pack_decode_gate_up, q), s.view(2, F2 // 32, 16).permute(1, 0, 2).reshape(F2).contiguous()
+
+
+def pack_decode_qkv_rope_fp8(wqkv):
+    """QKV rows -> (wp8 in the per-head rope tile order, scale_p in the same order)."""
+    q, s = _quantized(wqkv)
+    N = q.shape[0]
+    wp8 = _u8(pack_decode_qkv_rope, q)
+    idx = torch.tensor(_ROPE_TILE_ORDER, device=s.device)
+    return wp8, s.view(N // 128, 8, 16).index_select(1, idx).reshape(N).contiguous()
+
+
+def unpack_decode_weight_fp8(wp8, scale_p):
+    """-> (q [N, K] e4m3, scale [N]) in model row order."""
+    return _u8(unpack_decode_weight, wp8), scale_p
+
+
+def unpack_decode_gate_up_fp8(wp8, scale_p):
+    F2 = scale_p.shape[0]
+    return _u8(unpack_decode_gate_up, wp8), scale_p.view(F2 // 32, 2, 16).permute(1, 0, 2).reshape(F2)
+
+
+def unpack_decode_qkv_rope_fp8(wp8, scale_p):
+    N = scale_p.shape[0]
+    inv = torch.argsort(torch.tensor(_ROPE_TILE_ORDER)).to(scale_p.device)
+    return _u8(unpack_decode_qkv_rope, wp8), scale_p.view(N // 128, 8, 16).index_select(1, inv).reshape(N)
+
+
+def _dequant_packed(wp8, scale_p, dtype=torch.bfloat16):
+    """Packed bf16 fragments q * scale from the packed FP8 copy (layout unchanged)."""
+    T, S = wp8.shape[0], wp8.shape[1]
+    sc = scale_p.float().view(T, 1, 1, 16, 1)
+    return (wp8.float().view(T, S, 4, 16, 8) * sc).to(dtype).view(T, S, 64, 8)
+
+
+def decode_gemm_fp8(x: torch.Tensor, wp8: torch.Tensor, scale_p: torch.Tensor, epi: str = "plain",
+                    norm: bool = False, eps: float = 1e-5, resid: Optional[torch.Tensor] = None,
+                    out: Optional[torch.Tensor] = None, nt: int = 0, waves: int = 0, splits: int = 0) -> torch.Tensor:
+    """decode_gemm on the FP8 packed copy (pack_decode_weight_fp8 / pack_decode_gate_up_fp8):
+    equal, bit for bit, to decode_gemm on the bf16 pack of q * scale with the same config."""
+    M, K = x.shape
+    N = wp8.shape[0] * 16
+    code = DECODE_EPI[epi]
+    if not _on_gpu(x):
+        return decode_gemm(x, _dequant_packed(wp8, scale_p, x.dtype), epi, norm=norm, eps=eps, resid=resid, out=out,
+                           nt=nt, waves=waves, splits=splits)
+    if out is None:
+        out = torch.empty(M, N // 2 if code == 1 else N, dtype=x.dtype, device=x.device)
+    ws, cnt = decode_workspace(x.device)
+    if not require_native().decode_gemm_fp8(out, x, wp8, scale_p, resid, code, bool(norm), float(eps), int(nt),
+                                            int(waves), int(splits), ws, cnt):
+        raise ValueError(f"decode_gemm_fp8 does not handle M={M} N={N} K={K} epi={epi} nt={nt} waves={waves}")
+    return out
+
+
+def decode_qkv_rope_fp8(x: torch.Tensor, wp8: torch.Tensor, scale_p: torch.Tensor, eps: float, q_out: torch.Tensor,
+                        k_cache, v_cache, positions, slots, cos_sin, H: int, KV: int, splits: int = 0) -> torch.Tensor:
+    """decode_qkv_rope on the FP8 packed copy (pack_decode_qkv_rope_fp8)."""
+    if _on_gpu(x):
+        ws, cnt = decode_workspace(x.device)
+        require_native().decode_qkv_rope_fp8(x, wp8, scale_p, float(eps), q_out, k_cache, v_cache, positions, slots,
+                                             cos_sin, int(H), int(KV), int(splits), ws, cnt)
+        return q_out
+    return decode_qkv_rope(x, _dequant_packed(wp8, scale_p, x.dtype), eps, q_out, k_cache, v_cache, positions, slots,
+                           cos_sin, H, KV, splits=splits)
+
+
 # split-K slabs + tickets of the packed decode kernels (decode_gemm / decode_qkv_rope)
 DECODE_WS_FLOATS = 8 << 20  # 32 MB of split-K slabs per device
 _decode_ws = {}

@@ -726,3 +726,44 @@ def pack_mask(allowed) -> torch.Tensor:
     if pad:
         a = np.concatenate([a, np.zeros(pad, dtype=bool)])
     return torch.from_numpy(np.packbits(a, bitorder="little").view(np.int32).copy())
+
+
+# ---------------------------------------------------------------------------
+# FP8 (OCP e4m3fn) weight quantisation, per output channel, power-of-two scales
+# ---------------------------------------------------------------------------
+
+FP8_MAX = 448.0  # largest finite e4m3fn magnitude
+
+
+def _pow2_scale(amax: torch.Tensor) -> torch.Tensor:
+    """Smallest power of two s with amax <= 448 * s (fp32, exact); 1 where amax == 0."""
+    _, e = torch.frexp(amax / FP8_MAX)
+    s = torch.ldexp(torch.ones_like(amax), e)
+    # frexp's mantissa is in [0.5, 1): s is within one binade of the answer; settle it exactly
+    s = torch.where(amax > FP8_MAX * s, s * 2, s)
+    s = torch.where(amax <= FP8_MAX / 2 * s, s / 2, s)
+    return torch.where(amax > 0, s, torch.ones_like(s))
+
+
+def quantize_fp8_rows(w: torch.Tensor):
+    """[N, K] -> (q [N, K] float8_e4m3fn, scale [N] fp32) with w ~ q * scale[:, None].
+
+    scale_n = 2^ceil(log2(amax_n / 448)) (1 for an all-zero row); q = e4m3fn(w / scale_n),
+    round-to-nearest-even, saturating at +-448, so the NaN codes 0x7F / 0xFF never appear.
+    A row whose maximum would round DOWN to 224 (amax / scale in (224, 232]) takes the next
+    smaller scale instead: its maximum then saturates to 448 * scale / 2, the same value, and
+    every smaller element keeps one more bit. With that, max |q| of a non-zero row is always in
+    (224, 448] and quantising q * scale again returns the same q and scale.
+    q * scale is exactly representable in bf16 (3 mantissa bits times a power of two)."""
+    wf = w.float()
+    amax = wf.abs().amax(dim=1)
+    s = _pow2_scale(amax)
+    top = (amax / s).to(torch.float8_e4m3fn).float()  # the row maximum as it would be stored
+    s = torch.where((amax > 0) & (top <= FP8_MAX / 2), s / 2, s)
+    q = (wf / s[:, None]).clamp(-FP8_MAX, FP8_MAX).to(torch.float8_e4m3fn)
+    return q, s
+
+
+def dequantize_fp8_rows(q: torch.Tensor, scale: torch.Tensor, dtype=torch.bfloat16) -> torch.Tensor:
+    """q * scale per row, exact in bf16."""
+    return (q.float() * scale.float()[:, None]).to(dtype)

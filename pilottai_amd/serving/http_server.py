@@ -339,7 +339,13 @@ def create_app(llm, model_name: Optional[str] = None, engine=None) -> FastAPI:
 
     @app.get("/v1/models")
     async def models():
-        return {"object": "list", "data": [{"id": name, "object": "model", "owned_by": "pilottai_amd"}]}
+        entry = {"id": name, "object": "model", "owned_by": "pilottai_amd"}
+        eng = engine or getattr(llm, "engine", None)
+        model = getattr(eng, "model", None)
+        if model is not None:
+            entry["weight_quant"] = getattr(model, "weight_quant", None)
+            entry["fp8_decode"] = bool(getattr(model, "fp8_decode", False))
+        return {"object": "list", "data": [entry]}
 
     @app.post("/v1/chat/completions")
     async def chat(body: Dict[str, Any]):
@@ -506,14 +512,22 @@ def create_app(llm, model_name: Optional[str] = None, engine=None) -> FastAPI:
     return app
 
 
-def main():
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--model", default="llama-3-8b")
     ap.add_argument("--host", default="127.0.0.1")
     ap.add_argument("--port", type=int, default=8000)
     ap.add_argument("--schema", action="store_true", help="model-free SchemaLLM backend (no GPU)")
     ap.add_argument("--kv-gb", type=float, default=48.0)
-    a = ap.parse_args()
+    ap.add_argument("--weight-quant", choices=["fp8"], default=None,
+                    help="quantise the layer projections (fp8: e4m3, per-channel power-of-two scales)")
+    ap.add_argument("--no-fp8-decode", dest="fp8_decode", action="store_false",
+                    help="with --weight-quant fp8: keep decode steps on the bf16 kernels (no FP8 copy in HBM)")
+    return ap
+
+
+def main():
+    a = build_parser().parse_args()
     import uvicorn
 
     from pilottai_amd.core.config import LLMConfig
@@ -531,7 +545,8 @@ def main():
         eng = LLMEngine(EngineConfig(model=a.model if dev.type == "cuda" else "tiny",
                                      kv_cache_gb=a.kv_gb if dev.type == "cuda" else None,
                                      num_kv_blocks=None if dev.type == "cuda" else 1024,
-                                     freeze_heap=True), device=dev)
+                                     freeze_heap=True, weight_quant=a.weight_quant,
+                                     fp8_decode=a.fp8_decode), device=dev)
         eng.start()
         llm = LocalLLM(LLMConfig(model_name=eng.model_cfg.name, max_tokens=1024), engine=eng)
         app = create_app(llm, eng.model_cfg.name, engine=eng)
