@@ -15,6 +15,10 @@ int pa_rope_cache(void* q_out, void* k_cache, void* v_cache, const void* qkv, co
                   int block_size, int apply_rope, hipStream_t st);
 int pa_kv_copy(void* k_cache, void* v_cache, const int* n_copies, const int* copies, int max_copies,
                int layers, int num_blocks, int KV, long layer_stride, int block_size, hipStream_t st);
+int pa_kv_gather_blocks(void* k_cache, void* v_cache, const int* ids, int n, void* stage, int layers,
+                        int num_blocks, int KV, long layer_stride, int block_size, hipStream_t st);
+int pa_kv_scatter_blocks(void* k_cache, void* v_cache, const int* ids, int n, void* stage, int layers,
+                         int num_blocks, int KV, long layer_stride, int block_size, hipStream_t st);
 int pa_span_pool(const void* hn, const int* n_seg, const int* segs, int cap, float* pool, int T, int d, int slots,
                  hipStream_t st);
 int pa_silu_mul(void* out, const void* in, int T, int F, hipStream_t st);
@@ -242,6 +246,39 @@ void kv_copy(at::Tensor k_cache, at::Tensor v_cache, at::Tensor n_copies, at::Te
                       (int)max_copies, (int)layers, (int)blocks, (int)KV, (long)(blocks * KV * 2048), 16,
                       cur_stream()),
            "kv_copy");
+}
+
+// Host tier of the prefix cache (csrc/ops/kv_pages.hip): the pages of blocks ids[0:n] <-> records
+// 0..n-1 of `stage` [records, layers * 2 * KV * 2048] bf16; caches as for kv_copy
+static void kv_pages(at::Tensor& k_cache, at::Tensor& v_cache, at::Tensor& ids, int64_t n, at::Tensor& stage,
+                     bool gather) {
+  const char* name = gather ? "kv_gather_blocks" : "kv_scatter_blocks";
+  check_gpu(k_cache, "k_cache"); check_gpu(v_cache, "v_cache"); check_gpu(ids, "ids"); check_gpu(stage, "stage");
+  check_dtype(k_cache, at::kBFloat16, "k_cache"); check_dtype(v_cache, at::kBFloat16, "v_cache");
+  check_dtype(ids, at::kInt, "ids"); check_dtype(stage, at::kBFloat16, "stage");
+  TORCH_CHECK(k_cache.dim() == 6 && k_cache.size(3) == 16 && k_cache.size(4) == 16 && k_cache.size(5) == 8 &&
+                  k_cache.is_contiguous(),
+              "k_cache must be a contiguous [layers, blocks, KV, 16, 16, 8]");
+  TORCH_CHECK(v_cache.dim() == 5 && v_cache.size(3) == 128 && v_cache.size(4) == 16 && v_cache.is_contiguous() &&
+                  v_cache.size(0) == k_cache.size(0) && v_cache.size(1) == k_cache.size(1) &&
+                  v_cache.size(2) == k_cache.size(2),
+              "v_cache must be a contiguous [layers, blocks, KV, 128, 16] matching k_cache");
+  const int64_t layers = k_cache.size(0), blocks = k_cache.size(1), KV = k_cache.size(2);
+  const int64_t record = layers * 2 * KV * 2048;
+  TORCH_CHECK(n >= 0 && n <= ids.numel() && ids.is_contiguous(), name, ": n must lie in [0, len(ids)]");
+  TORCH_CHECK(stage.dim() == 2 && stage.size(1) == record && stage.is_contiguous() && n <= stage.size(0), name,
+              ": stage must be a contiguous [>= n, layers * 2 * KV * 2048] bf16 tensor");
+  TORCH_CHECK(layers * 2 <= 65535 && blocks < (1ll << 31) && n < (1ll << 31), name, ": grid too large");
+  auto fn = gather ? pa_kv_gather_blocks : pa_kv_scatter_blocks;
+  check_rc(fn(k_cache.data_ptr(), v_cache.data_ptr(), ids.data_ptr<int>(), (int)n, stage.data_ptr(), (int)layers,
+              (int)blocks, (int)KV, (long)(blocks * KV * 2048), 16, cur_stream()),
+           name);
+}
+void kv_gather_blocks(at::Tensor k_cache, at::Tensor v_cache, at::Tensor ids, int64_t n, at::Tensor stage) {
+  kv_pages(k_cache, v_cache, ids, n, stage, true);
+}
+void kv_scatter_blocks(at::Tensor k_cache, at::Tensor v_cache, at::Tensor ids, int64_t n, at::Tensor stage) {
+  kv_pages(k_cache, v_cache, ids, n, stage, false);
 }
 
 // hn [T, d] bf16; n_seg: one device word; segs: device words (first_row, n_rows, slot, init) x capacity;
@@ -1562,6 +1599,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("sample_workspace_floats", &sample_workspace_floats);
   m.def("patch_pending_ids", &patch_pending_ids);
   m.def("kv_copy", &kv_copy);
+  m.def("kv_gather_blocks", &kv_gather_blocks);
+  m.def("kv_scatter_blocks", &kv_scatter_blocks);
   m.def("span_pool", &span_pool);
   m.def("sample_partials", &sample_partials, py::arg("workspace"), py::arg("logits"), py::arg("vocab_offset"),
         py::arg("temperature"), py::arg("mask_class"), py::arg("class_masks"), py::arg("seeds"),

@@ -166,8 +166,8 @@ PYBIND11_MODULE(_runtime, m) {
       });
 
   py::class_<BlockManager>(m, "BlockManager")
-      .def(py::init<int32_t, int32_t, bool>(), py::arg("num_blocks"), py::arg("block_size") = 16,
-           py::arg("prefix_caching") = true)
+      .def(py::init<int32_t, int32_t, bool, int32_t>(), py::arg("num_blocks"), py::arg("block_size") = 16,
+           py::arg("prefix_caching") = true, py::arg("host_slots") = 0)
       .def("allocate", [](BlockManager& bm, int32_t n) -> py::object {
         std::vector<int32_t> out;
         if (!bm.allocate(n, out)) return py::none();
@@ -201,7 +201,26 @@ PYBIND11_MODULE(_runtime, m) {
       }, py::arg("parent"), py::arg("tokens"), py::arg("max_j") = 16, py::arg("min_j") = 1)
       .def_property_readonly("num_free", &BlockManager::num_free)
       .def_property_readonly("num_cached", &BlockManager::num_cached)
-      .def_property_readonly("num_donors", &BlockManager::num_donors);
+      .def_property_readonly("num_donors", &BlockManager::num_donors)
+      // host tier: slot holding the block (-1: none), no side effects
+      .def("host_peek", [](const BlockManager& bm, uint64_t hash, const std::vector<int32_t>& toks) {
+        if ((int32_t)toks.size() != bm.block_size()) throw std::invalid_argument("host_peek takes one block of tokens");
+        return bm.host_peek(hash, toks.data());
+      })
+      .def("restore", &BlockManager::restore)
+      // -> (spills [(block, slot)], fills [(slot, block)])
+      .def("take_moves", [](BlockManager& bm) {
+        std::vector<KvMove> sp, fi;
+        bm.take_moves(sp, fi);
+        py::list a, b;
+        for (const KvMove& m : sp) a.append(py::make_tuple(m.block, m.slot));
+        for (const KvMove& m : fi) b.append(py::make_tuple(m.slot, m.block));
+        return py::make_tuple(a, b);
+      })
+      .def_property_readonly("num_host_cached", &BlockManager::num_host_cached)
+      .def_property_readonly("host_hit_blocks", &BlockManager::host_hit_blocks)
+      .def_property_readonly("host_spilled_blocks", &BlockManager::host_spilled_blocks)
+      .def_property_readonly("host_evicted_blocks", &BlockManager::host_evicted_blocks);
 
   py::class_<Scheduler>(m, "Scheduler")
       .def(py::init([](const py::dict& d) {
@@ -236,6 +255,13 @@ PYBIND11_MODULE(_runtime, m) {
         if (d.contains("small_step_target")) c.small_step_target = d["small_step_target"].cast<int32_t>();
         if (d.contains("penalty_slots")) c.penalty_slots = d["penalty_slots"].cast<int32_t>();
         if (d.contains("embed_span_slots")) c.embed_span_slots = d["embed_span_slots"].cast<int32_t>();
+        if (d.contains("host_slots")) c.host_slots = d["host_slots"].cast<int32_t>();
+        if (d.contains("host_cache_step_blocks"))
+          c.host_cache_step_blocks = d["host_cache_step_blocks"].cast<int32_t>();
+        if (c.host_slots < 0 || c.host_cache_step_blocks < 0)
+          throw std::invalid_argument("scheduler: host_slots and host_cache_step_blocks must not be negative");
+        if (c.host_slots > 0 && !c.prefix_caching)
+          throw std::invalid_argument("scheduler: the host tier (host_slots > 0) needs prefix_caching");
         if (d.contains("eos_ids")) c.eos_ids = d["eos_ids"].cast<std::vector<int32_t>>();
         return std::make_unique<Scheduler>(c);
       }))
@@ -343,6 +369,22 @@ PYBIND11_MODULE(_runtime, m) {
       .def_property_readonly_static("FINISH_SCORE", [](const py::object&) { return (int)FINISH_SCORE; })
       .def("abort", &Scheduler::abort)
       .def("take_embed_resets", &Scheduler::take_embed_resets)
+      // host tier: -> (spills [(block, slot)], fills [(slot, block)]) of the last schedule() call;
+      // run all spills, then all fills, before the step
+      .def("take_kv_moves", [](Scheduler& s) {
+        const Scheduler::KvMoves m = s.take_kv_moves();
+        py::list a, b;
+        for (const KvMove& x : m.spills) a.append(py::make_tuple(x.block, x.slot));
+        for (const KvMove& x : m.fills) b.append(py::make_tuple(x.slot, x.block));
+        return py::make_tuple(a, b);
+      })
+      .def_property_readonly("host_hit_blocks", &Scheduler::host_hit_blocks)
+      .def_property_readonly("host_spilled_blocks", &Scheduler::host_spilled_blocks)
+      .def_property_readonly("host_evicted_blocks", &Scheduler::host_evicted_blocks)
+      .def_property_readonly("num_host_cached", &Scheduler::num_host_cached)
+      // [(tier, id)]: tier 0 = device block, 1 = host slot; stops at the first miss
+      .def("prefix_blocks", &Scheduler::prefix_blocks)
+      .def("planned_ids", &Scheduler::planned_ids)
       .def("num_free_embed_rows", &Scheduler::num_free_embed_rows)
       .def_property_readonly("num_free_penalty_slots", &Scheduler::num_free_penalty_slots)
       .def_property_readonly("prefix_defers", &Scheduler::prefix_defers)

@@ -20,8 +20,9 @@ uint64_t hash_block(uint64_t parent, const int32_t* tokens, int n) {
   return h ? h : 1;
 }
 
-BlockManager::BlockManager(int32_t num_blocks, int32_t block_size, bool prefix_caching)
-    : num_blocks_(num_blocks), block_size_(block_size), prefix_caching_(prefix_caching) {
+BlockManager::BlockManager(int32_t num_blocks, int32_t block_size, bool prefix_caching, int32_t host_slots)
+    : num_blocks_(num_blocks), block_size_(block_size), prefix_caching_(prefix_caching),
+      host_slots_(prefix_caching ? std::max(0, host_slots) : 0) {
   reset();
 }
 
@@ -43,6 +44,129 @@ void BlockManager::reset() {
   free_list_.clear();
   free_list_.reserve(num_blocks_);
   for (int32_t b = num_blocks_ - 1; b >= 0; --b) free_list_.push_back(b);
+  // the host tier goes with the cache it extends; moves not taken yet name blocks that no
+  // longer mean anything
+  spills_.clear();
+  fills_.clear();
+  h_pin_.assign(host_slots_, 0);
+  reset_host();
+}
+
+void BlockManager::reset_host() {
+  if (host_slots_ <= 0) return;
+  h_hash_.resize(host_slots_, 0);
+  h_parent_.resize(host_slots_, 0);
+  h_tokens_.resize(host_slots_);
+  h_used_.resize(host_slots_, 0);
+  host_pos_.resize(host_slots_, host_lru_.end());
+  for (int32_t s = 0; s < host_slots_; ++s) {
+    if (!h_used_[s] || h_pin_[s] > 0) continue;
+    host_dir_.erase(h_hash_[s]);
+    host_lru_.erase(host_pos_[s]);
+    h_used_[s] = 0;
+    h_tokens_[s].clear();
+  }
+  host_free_.clear();
+  for (int32_t s = host_slots_ - 1; s >= 0; --s)
+    if (!h_used_[s]) host_free_.push_back(s);
+}
+
+void BlockManager::host_touch(int32_t slot) {
+  host_lru_.erase(host_pos_[slot]);
+  host_lru_.push_back(slot);
+  host_pos_[slot] = std::prev(host_lru_.end());
+}
+
+int32_t BlockManager::take_host_slot() {
+  if (!host_free_.empty()) {
+    const int32_t s = host_free_.back();
+    host_free_.pop_back();
+    return s;
+  }
+  for (const int32_t s : host_lru_) {
+    if (h_pin_[s] > 0) continue;
+    host_dir_.erase(h_hash_[s]);
+    host_lru_.erase(host_pos_[s]);
+    h_used_[s] = 0;
+    ++host_evicted_;
+    return s;
+  }
+  return -1;
+}
+
+void BlockManager::spill(int32_t b) {
+  if (host_slots_ <= 0 || !hashed_[b] || (int32_t)tokens_[b].size() != block_size_) return;
+  auto it = host_dir_.find(hash_[b]);
+  if (it != host_dir_.end()) {  // inclusive tier: the slot already holds these bytes
+    if (h_tokens_[it->second] == tokens_[b]) host_touch(it->second);
+    return;
+  }
+  const int32_t s = take_host_slot();
+  if (s < 0) return;  // every slot is pinned: dropped, as without the tier
+  h_hash_[s] = hash_[b];
+  h_parent_[s] = dparent_[b];
+  h_tokens_[s] = tokens_[b];
+  h_used_[s] = 1;
+  host_lru_.push_back(s);
+  host_pos_[s] = std::prev(host_lru_.end());
+  host_dir_.emplace(hash_[b], s);
+  ++h_pin_[s];
+  spills_.push_back({b, s});
+  ++host_spilled_;
+}
+
+int32_t BlockManager::peek(uint64_t hash, const int32_t* tokens) const {
+  if (!prefix_caching_) return -1;
+  auto it = cache_.find(hash);
+  if (it == cache_.end()) return -1;
+  const int32_t b = it->second;
+  if ((int32_t)tokens_[b].size() != block_size_ ||
+      std::memcmp(tokens_[b].data(), tokens, sizeof(int32_t) * block_size_) != 0)
+    return -1;
+  return b;
+}
+
+int32_t BlockManager::host_peek(uint64_t hash, const int32_t* tokens) const {
+  if (host_slots_ <= 0) return -1;
+  auto it = host_dir_.find(hash);
+  if (it == host_dir_.end()) return -1;
+  const int32_t s = it->second;
+  if ((int32_t)h_tokens_[s].size() != block_size_ ||
+      std::memcmp(h_tokens_[s].data(), tokens, sizeof(int32_t) * block_size_) != 0)
+    return -1;
+  return s;
+}
+
+void BlockManager::host_pin(int32_t slot, int32_t d) {
+  if (slot < 0 || slot >= host_slots_) return;
+  h_pin_[slot] = std::max(0, h_pin_[slot] + d);
+}
+
+int32_t BlockManager::restore(int32_t slot) {
+  if (slot < 0 || slot >= host_slots_ || !h_used_[slot]) return -1;
+  if (cache_.count(h_hash_[slot])) return -1;
+  ++h_pin_[slot];  // the allocation below may evict into the tier: not into this slot
+  std::vector<int32_t> out;
+  if (!allocate(1, out)) {
+    --h_pin_[slot];
+    return -1;
+  }
+  const int32_t b = out[0];
+  register_block(b, h_hash_[slot], h_tokens_[slot].data(), h_parent_[slot]);
+  reused_[b] = 1;
+  host_touch(slot);
+  fills_.push_back({b, slot});  // the pin stays until the move is taken
+  ++host_hits_;
+  return b;
+}
+
+void BlockManager::take_moves(std::vector<KvMove>& spills, std::vector<KvMove>& fills) {
+  for (const KvMove& m : spills_) host_pin(m.slot, -1);
+  for (const KvMove& m : fills_) host_pin(m.slot, -1);
+  spills.swap(spills_);
+  fills.swap(fills_);
+  spills_.clear();
+  fills_.clear();
 }
 
 void BlockManager::lru_remove(int32_t b) {
@@ -99,6 +223,7 @@ void BlockManager::evict_one() {
   const int list = lru_[0].empty() ? 1 : 0;  // never-reused blocks first
   const int32_t b = lru_[list].front();
   lru_remove(b);
+  spill(b);
   forget(b);
   free_list_.push_back(b);
 }

@@ -18,6 +18,15 @@
 // the hash chain inside a block asks match_head() for the listed block sharing the longest
 // head with it and copies those slots (csrc/ops/kv_copy.hip) instead of computing them. A
 // partial tail block is evictable like a hashed block once its last user releases it.
+//
+// Host tier (host_slots > 0): a second, host-resident directory hash -> slot under the device
+// cache. Evicting a hashed full block lists a spill (block, slot) unless its hash is already in
+// the directory (the tier is inclusive: a restored block is never spilled twice); a chain that
+// continues into the directory gets a fresh device block per host hit and a fill (slot, block).
+// The manager only plans the moves: the caller takes them (take_moves) and runs every spill,
+// then every fill, before the device blocks are read or written again. A slot named by a move
+// not yet taken is pinned: it is neither evicted from the tier nor given to another spill.
+// Partial tail donors are not spilled.
 #pragma once
 #include <cstdint>
 #include <list>
@@ -28,9 +37,13 @@ namespace rt {
 
 uint64_t hash_block(uint64_t parent, const int32_t* tokens, int n);
 
+struct KvMove {
+  int32_t block, slot;  // device block, host slot
+};
+
 class BlockManager {
  public:
-  BlockManager(int32_t num_blocks, int32_t block_size, bool prefix_caching);
+  BlockManager(int32_t num_blocks, int32_t block_size, bool prefix_caching, int32_t host_slots = 0);
   int32_t block_size() const { return block_size_; }
   int32_t num_blocks() const { return num_blocks_; }
   int32_t num_free() const { return (int32_t)(free_list_.size() + lru_[0].size() + lru_[1].size()); }
@@ -57,9 +70,32 @@ class BlockManager {
   int32_t ref_count(int32_t block) const { return ref_[block]; }
   int32_t num_donors() const { return num_donors_; }
   void reset();
+  // ---- host tier
+  int32_t host_slots() const { return host_slots_; }
+  int32_t num_host_cached() const { return (int32_t)host_dir_.size(); }
+  // the device block / host slot holding exactly `tokens` under `hash`, or -1: no reference is
+  // taken and no LRU order changes
+  int32_t peek(uint64_t hash, const int32_t* tokens) const;
+  int32_t host_peek(uint64_t hash, const int32_t* tokens) const;
+  // keep `slot` (d = +1) from being evicted while a lookup that found it goes on; d = -1 undoes it
+  void host_pin(int32_t slot, int32_t d);
+  // Bring the block in `slot` back: a device block is allocated (evicting, and so perhaps
+  // spilling, as any allocation), registered under the slot's hash as a reused block with one
+  // reference taken, and the fill (slot, block) is listed. -1 when no block can be allocated or
+  // the hash is resident on the device already.
+  int32_t restore(int32_t slot);
+  // the moves planned since the last call, in planning order; unpins their slots
+  void take_moves(std::vector<KvMove>& spills, std::vector<KvMove>& fills);
+  void reset_host();  // forget every slot that no pending move names
+  int64_t host_hit_blocks() const { return host_hits_; }
+  int64_t host_spilled_blocks() const { return host_spilled_; }
+  int64_t host_evicted_blocks() const { return host_evicted_; }
 
  private:
   void evict_one();
+  void spill(int32_t b);       // evict_one: list the block for the host tier, if it is one to keep
+  int32_t take_host_slot();    // a free slot, or the oldest unpinned one (its entry is dropped), or -1
+  void host_touch(int32_t slot);
   void donor_add(int32_t b, uint64_t parent, int32_t fill);
   void donor_drop(int32_t b);
   void forget(int32_t b);  // the block leaves the cache: hash entry, donor entry, tokens
@@ -83,6 +119,18 @@ class BlockManager {
   std::vector<uint64_t> dparent_;
   std::vector<int32_t> fill_;
   int32_t num_donors_ = 0;
+  // host tier: slot -> hash, parent hash and verification tokens of the block it holds
+  int32_t host_slots_ = 0;
+  std::unordered_map<uint64_t, int32_t> host_dir_;
+  std::vector<uint64_t> h_hash_, h_parent_;
+  std::vector<std::vector<int32_t>> h_tokens_;
+  std::vector<int32_t> h_pin_;      // pending moves and lookups in progress that name the slot
+  std::vector<char> h_used_;
+  std::vector<int32_t> host_free_;
+  std::list<int32_t> host_lru_;     // slots in use, front = oldest
+  std::vector<std::list<int32_t>::iterator> host_pos_;
+  std::vector<KvMove> spills_, fills_;
+  int64_t host_hits_ = 0, host_spilled_ = 0, host_evicted_ = 0;
 };
 
 }  // namespace rt

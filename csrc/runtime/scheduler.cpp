@@ -32,7 +32,7 @@ static LogprobRecord forced_record(int32_t tok, int32_t n) {
 }
 
 Scheduler::Scheduler(const SchedulerConfig& cfg)
-    : cfg_(cfg), bm_(cfg.num_blocks, cfg.block_size, cfg.prefix_caching) {
+    : cfg_(cfg), bm_(cfg.num_blocks, cfg.block_size, cfg.prefix_caching, cfg.host_slots) {
   StepLayout& L = lay_;
   L.max_tokens = cfg.max_num_batched_tokens;
   L.max_seqs = cfg.max_num_seqs;
@@ -298,14 +298,56 @@ void Scheduler::match_prefix(Sequence* s) {
     // logits row) itself, everything before it may come from the cache
     const int32_t n_full = (s->scoring() ? s->score_from - 1 : (int32_t)s->tokens.size() - 1) / B;
     uint64_t parent = 0;
-    for (int32_t b = 0; b < n_full; ++b) {
-      const int32_t* t = s->tokens.data() + (size_t)b * B;
-      const uint64_t h = hash_block(parent, t, B);
-      const int32_t blk = bm_.lookup(h, t);
-      if (blk < 0) break;
-      s->blocks.push_back(blk);
-      s->block_hashes.push_back(h);
-      parent = h;
+    if (cfg_.host_slots <= 0) {
+      for (int32_t b = 0; b < n_full; ++b) {
+        const int32_t* t = s->tokens.data() + (size_t)b * B;
+        const uint64_t h = hash_block(parent, t, B);
+        const int32_t blk = bm_.lookup(h, t);
+        if (blk < 0) break;
+        s->blocks.push_back(blk);
+        s->block_hashes.push_back(h);
+        parent = h;
+      }
+    } else {
+      // Two passes. First find how far the chain goes on the device or in the host tier, taking
+      // the device references (and pinning the host slots): only then is a device block
+      // allocated per host hit, so that bringing the head of a chain back never evicts a
+      // resident block -- or a host slot -- further along the same chain.
+      struct Hit {
+        uint64_t h;
+        int32_t blk, slot;
+      };
+      std::vector<Hit> hits;
+      int32_t host_hits = 0;
+      for (int32_t b = 0; b < n_full; ++b) {
+        const int32_t* t = s->tokens.data() + (size_t)b * B;
+        const uint64_t h = hash_block(parent, t, B);
+        const int32_t blk = bm_.lookup(h, t);
+        int32_t slot = -1;
+        if (blk < 0) {
+          if (host_hits >= fills_left_ || (slot = bm_.host_peek(h, t)) < 0) break;  // the cap ends the chain
+          bm_.host_pin(slot, 1);
+          ++host_hits;
+        }
+        hits.push_back({h, blk, slot});
+        parent = h;
+      }
+      const int32_t watermark = std::max(1, cfg_.num_blocks / 100);
+      bool ended = false;
+      for (const Hit& x : hits) {
+        int32_t blk = x.blk;
+        if (ended) {  // behind a block that could not be brought back: not part of the chain
+          if (blk >= 0) bm_.release(blk);
+        } else if (blk < 0) {
+          blk = bm_.num_free() > watermark ? bm_.restore(x.slot) : -1;
+          if (blk < 0) ended = true;
+          else --fills_left_;
+        }
+        if (x.slot >= 0) bm_.host_pin(x.slot, -1);
+        if (ended) continue;
+        s->blocks.push_back(blk);
+        s->block_hashes.push_back(x.h);
+      }
     }
   }
   s->num_computed = (int32_t)s->blocks.size() * B;
@@ -469,6 +511,7 @@ int32_t Scheduler::schedule(int32_t* buf, int32_t buf_words) {
     throw std::invalid_argument("scheduler: a request with spans needs a step buffer of "
                                 "layout().span_total words, stated as schedule()'s second argument");
   copies_ok_ = buf_words >= L.copy_total;
+  fills_left_ = std::max(0, cfg_.host_cache_step_blocks);
   drafts_ok_ = buf_words >= L.spec_total && plans_.empty();
   last_plan_.clear();
   // rows of the step (sampling rows + scoring rows) never exceed max_num_seqs. A scoring request
@@ -1656,8 +1699,42 @@ std::vector<int32_t> Scheduler::planned_draft(int64_t id) const {
   return {};
 }
 
+Scheduler::KvMoves Scheduler::take_kv_moves() {
+  KvMoves m;
+  bm_.take_moves(m.spills, m.fills);
+  return m;
+}
+
+std::vector<std::pair<int32_t, int32_t>> Scheduler::prefix_blocks(const std::vector<int32_t>& tokens) const {
+  std::vector<std::pair<int32_t, int32_t>> out;
+  const int32_t B = cfg_.block_size;
+  uint64_t parent = 0;
+  for (size_t b = 0; (b + 1) * B <= tokens.size(); ++b) {
+    const int32_t* t = tokens.data() + b * B;
+    const uint64_t h = hash_block(parent, t, B);
+    int32_t id = bm_.peek(h, t);
+    if (id >= 0) {
+      out.emplace_back(0, id);
+    } else if ((id = bm_.host_peek(h, t)) >= 0) {
+      out.emplace_back(1, id);
+    } else {
+      break;
+    }
+    parent = h;
+  }
+  return out;
+}
+
+std::vector<int64_t> Scheduler::planned_ids() const {
+  std::vector<int64_t> ids;
+  if (!plans_.empty())
+    for (const Planned& p : plans_.back().rows) ids.push_back(p.s->id);
+  return ids;
+}
+
 void Scheduler::reset_prefix_cache() {
   if (running_.empty()) bm_.reset();
+  else bm_.reset_host();
 }
 
 }  // namespace rt

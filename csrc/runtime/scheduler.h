@@ -98,6 +98,12 @@ struct SchedulerConfig {
   // device accumulator rows for span pooling (csrc/ops/span_pool.hip): an embedding request with
   // spans holds one per span from admission to finish
   int32_t embed_span_slots = 256;
+  // host tier under the prefix cache (block_manager.h): slots of pinned host memory, one block
+  // each; 0 = off, and then no code path changes. A prompt's chain may continue into the tier:
+  // at most host_cache_step_blocks blocks are brought back per schedule() call (the rest of the
+  // chain is computed), and the caller runs the moves of every call (take_kv_moves).
+  int32_t host_slots = 0;
+  int32_t host_cache_step_blocks = 256;
   std::vector<int32_t> eos_ids;
 };
 
@@ -456,6 +462,24 @@ class Scheduler {
   // Pooling rows whose embedding request was preempted in the last schedule() (it restarts
   // from token 0): the caller clears them before running the step.
   std::vector<int32_t> take_embed_resets();
+  // The host tier's moves planned by the last schedule() call: spills (device block -> host slot)
+  // and fills (host slot -> device block), each in planning order. The caller executes all
+  // spills, then all fills, before the step runs -- after every schedule() call, one that
+  // returned 0 tokens included. Both are empty without a host tier.
+  struct KvMoves {
+    std::vector<KvMove> spills, fills;
+  };
+  KvMoves take_kv_moves();
+  int64_t host_hit_blocks() const { return bm_.host_hit_blocks(); }
+  int64_t host_spilled_blocks() const { return bm_.host_spilled_blocks(); }
+  int64_t host_evicted_blocks() const { return bm_.host_evicted_blocks(); }
+  int32_t num_host_cached() const { return bm_.num_host_cached(); }
+  // Where the leading full blocks of `tokens` are: (tier, id) per block of the hash chain, tier
+  // 0 = device block, 1 = host slot, up to the first miss. No reference is taken and no LRU
+  // order changes (diagnostics).
+  std::vector<std::pair<int32_t, int32_t>> prefix_blocks(const std::vector<int32_t>& tokens) const;
+  // the request of each row (sequence entry) of the step scheduled last, for diagnostics
+  std::vector<int64_t> planned_ids() const;
   struct SeqState {
     int64_t id;
     bool running, embed;
@@ -539,6 +563,7 @@ class Scheduler {
   int64_t stat_prefix_defers_ = 0;
   int64_t stat_partial_tokens_ = 0, stat_same_step_ = 0;
   bool copies_ok_ = false;  // the buffer of the schedule() call in progress holds the copy list
+  int32_t fills_left_ = 0;  // host-tier fills the schedule() call in progress may still plan
   uint64_t prefix_key(const Sequence* s) const;
 };
 

@@ -94,6 +94,10 @@ class LLMConfig(BaseModel):
     # provider "local": weight quantisation of the engine this model is served by (None, "fp8":
     # EngineConfig.weight_quant); the model-free and HTTP backends ignore it
     weight_quant: Optional[str] = None
+    # provider "local": pinned host memory (GiB) of the engine's host KV tier, where blocks evicted
+    # from the prefix cache are kept and copied back from (EngineConfig.host_cache_gb; None = the
+    # engine's own setting, 0 = off); the model-free and HTTP backends ignore it
+    host_cache_gb: Optional[float] = Field(default=None, ge=0.0)
     max_tokens: int = Field(default=2000, gt=0)
     function_calling_model: Optional[str] = None
     system_template: Optional[str] = None

@@ -30,12 +30,14 @@ nothing on the host has to be kept consistent between ranks.
 from __future__ import annotations
 
 import logging
+import math
 import os
 import queue
 import sys
 from collections import deque
 import threading
 import time
+import weakref
 from dataclasses import dataclass, field
 from numbers import Integral
 from typing import Any, Callable, Dict, List, Mapping, Optional, Sequence, Tuple, Union
@@ -60,6 +62,15 @@ log = logging.getLogger("pilottai_amd.engine")
 # the spacing bounds the padded (wasted) work: 16-token steps up to 512 (graph padding 1.9 ->
 # 1.1 % of step tokens at 64 workers; profiles/r2_buckets16_ab.jsonl), 64 up to 2048
 # (prefill-heavy agent steps sit at 400-1000 tokens).
+def _unregister_pool(pool: torch.Tensor):
+    try:
+        torch.cuda.cudart().cudaHostUnregister(pool.data_ptr())
+    except Exception:  # interpreter shutdown: the runtime is gone, and the registration with it
+        pass
+
+
+HOST_STAGE_RECORDS = 16  # records of the host tier's device staging buffer (2 MiB each on Llama-3-8B)
+
 DEFAULT_BUCKETS = ([8, 16, 32, 48, 64, 80] + list(range(96, 513, 16)) + list(range(576, 2049, 64))
                    + [3072, 4096, 6144, 8192])
 
@@ -85,6 +96,15 @@ class EngineConfig:
     # the best cached block instead of computing it (scheduler.h partial_block_reuse; the step
     # graph's first kernel, csrc/ops/kv_copy.hip). TP = 1 only.
     partial_block_reuse: bool = os.environ.get("PILOTTAI_PREFIX_PARTIAL", "1") != "0"
+    # host tier under the prefix cache (block_manager.h "Host tier", csrc/ops/kv_pages.hip):
+    # evicted full blocks are spilled to this much pinned host memory and copied back when a
+    # prompt's hash chain reaches them, instead of being computed again. 0 = off (nothing
+    # changes). host_cache_blocks, when given, sets the size in blocks instead (tests);
+    # host_cache_step_blocks caps the blocks brought back per step (the rest of the chain is
+    # computed). TP = 1 and the plain (not pipelined) loop only; needs prefix_caching.
+    host_cache_gb: float = 0.0
+    host_cache_blocks: Optional[int] = None
+    host_cache_step_blocks: int = 256
     # waiting embedding requests are admitted before waiting generation prompts (scheduler.h)
     embed_first: bool = os.environ.get("PILOTTAI_EMBED_FIRST", "1") != "0"
     split_decode: bool = True
@@ -282,6 +302,7 @@ class LLMEngine:
             ops.require_native()
             torch.cuda.set_device(self.device)
         self.tp = tp or TPGroup.single()
+        self._check_host_cache(cfg, self.tp.size)
         self.tok = tokenizer or get_tokenizer()
         self.grammar = GrammarCompiler(self.tok, reply_tokens=cfg.reply_tokens)
         self.model_cfg = get_config(cfg.model)
@@ -337,6 +358,19 @@ class LLMEngine:
             nb = int(t.item())
         self.kv = KVCache(mc.num_layers, nb, kv_local, self.device, block_size=cfg.block_size)
         self.num_kv_blocks = nb
+        # ---- host tier: a pinned pool of one record (every layer's K and V pages of a block)
+        # per slot, and a small device staging buffer that spills and fills share
+        hb = cfg.host_cache_blocks if cfg.host_cache_blocks is not None \
+            else int(float(cfg.host_cache_gb) * (1 << 30)) // bpb
+        self.host_cache_blocks = int(hb)
+        self.kv_block_bytes = bpb
+        self._host_pool = self._host_stage = None
+        if hb > 0:
+            if cfg.block_size != 16:
+                raise ValueError("the host KV tier needs block_size 16")
+            rec = bpb // 2  # bf16 elements of a record
+            self._host_pool = self._pinned_pool(hb, rec)
+            self._host_stage = torch.empty(HOST_STAGE_RECORDS, rec, dtype=torch.bfloat16, device=self.device)
         # ---- native scheduler + step buffers
         # the model runs 8-wave decode attention on the fused decode path only, keyed on the
         # graph bucket: the scheduler's whole-context (unsplit) items for small steps must
@@ -369,6 +403,7 @@ class LLMEngine:
             "decode_part_target": int(cfg.decode_part_target),
             "penalty_slots": max(0, min(int(cfg.max_num_seqs), int(cfg.penalty_slots))),
             "embed_span_slots": max(0, int(cfg.embed_span_slots)),
+            "host_slots": self.host_cache_blocks, "host_cache_step_blocks": int(cfg.host_cache_step_blocks),
             "eos_ids": list(self.tok.eos_ids)})
         L = self.L = self.sched.layout()
         pin = self.on_gpu
@@ -515,7 +550,7 @@ class LLMEngine:
                       "embed_requests": 0, "embed_tokens": 0,
                       "busy_s": 0.0, "prefill_tokens": 0, "decode_steps": 0, "graph_replays": 0, "graph_captures": 0,
                       "bucket_tokens": 0, "host_sched_s": 0.0, "host_launch_s": 0.0, "device_wait_s": 0.0,
-                      "host_commit_s": 0.0, "host_deliver_s": 0.0}
+                      "host_commit_s": 0.0, "host_deliver_s": 0.0, "host_move_s": 0.0}
         self.bucket_hist: Dict[int, list] = {}  # bucket -> [steps, seconds]
         # called on the engine thread right after a step is launched with its token count (the
         # memory batcher co-schedules its index scans with compute-bound steps, memory/batcher.py)
@@ -1520,6 +1555,9 @@ class LLMEngine:
         with trace_range("engine.schedule"):
             T = self.sched.schedule(self._host_ptr, self._host_meta.numel())
         t_sched = time.perf_counter()
+        t_moves = 0.0  # counted in host_move_s, not in host_launch_s
+        if self._host_pool is not None:  # after every schedule(), one that plans no step included
+            t_moves = self._run_kv_moves()
         if T == 0:
             self._flush_deliveries()
             if self.sched.num_running == 0 and self.sched.num_waiting > 0:
@@ -1601,7 +1639,7 @@ class LLMEngine:
         st = self.stats
         # host-side phases: schedule, metadata copy + launch, device wait, commit
         st["host_sched_s"] += t_sched - t0
-        st["host_launch_s"] += t_launch - t_sched
+        st["host_launch_s"] += t_launch - t_sched - t_moves
         st["device_wait_s"] += t_sync - t_launch
         st["steps"] += 1
         st["tokens"] += T
@@ -1618,6 +1656,95 @@ class LLMEngine:
         if not self.sched.has_work():
             self._flush_deliveries()  # nothing to overlap with: deliver now
         return True
+
+    # ------------------------------------------------------------- host KV tier
+    @staticmethod
+    def _check_host_cache(cfg: "EngineConfig", tp_size: int):
+        gb, nb, cap = cfg.host_cache_gb, cfg.host_cache_blocks, cfg.host_cache_step_blocks
+        if gb is None or not math.isfinite(float(gb)) or float(gb) < 0 or (nb is not None and int(nb) < 0):
+            raise ValueError(f"host_cache_gb / host_cache_blocks must not be negative ({gb!r}, {nb!r})")
+        if int(cap) < 0:
+            raise ValueError(f"host_cache_step_blocks must not be negative, not {cap!r}")
+        if not (int(nb) if nb is not None else float(gb) > 0):
+            return
+        if not cfg.prefix_caching:
+            raise ValueError("the host KV tier (host_cache_gb) extends the prefix cache: it needs prefix_caching")
+        if tp_size > 1:
+            raise ValueError("the host KV tier (host_cache_gb) is not supported on a tensor-parallel (TP > 1) engine")
+        if cfg.async_steps:
+            raise ValueError("the host KV tier (host_cache_gb) is not supported on an async_steps engine")
+
+    def _pinned_pool(self, slots: int, rec: int) -> torch.Tensor:
+        """The host tier's pool [slots, rec] bf16, page-locked at exactly its size: the bytes are
+        allocated pageable and registered with the runtime, because torch's pinned allocator may
+        round a request of this size up (to the next power of two) and host_cache_gb is a
+        promise about memory. Raises an error that names the size; the registration is undone
+        when the engine is collected."""
+        nbytes = slots * rec * 2
+        what = f"{nbytes / 2**30:.2f} GiB of pinned host memory ({slots} blocks of {rec * 2} bytes)"
+        try:
+            pool = torch.empty(slots, rec, dtype=torch.bfloat16)
+        except RuntimeError as e:
+            raise RuntimeError(f"host KV tier: cannot allocate {what}: {e}") from e
+        if not self.on_gpu:
+            return pool
+        rt = torch.cuda.cudart()
+        rc = int(rt.cudaHostRegister(pool.data_ptr(), nbytes, 0))
+        if rc != 0:
+            raise RuntimeError(f"host KV tier: cannot page-lock {what}: runtime error {rc}")
+        weakref.finalize(self, _unregister_pool, pool)
+        if not pool.is_pinned():
+            raise RuntimeError(f"host KV tier: {what} were registered but do not read as pinned")
+        return pool
+
+    def _run_kv_moves(self) -> float:
+        """-> host seconds spent. Execute the moves of the schedule() call just made, on the engine's stream and outside
+        the step graphs: every spill (gather into the staging buffer, one async copy per record
+        into its host slot), then every fill (one async copy per record out of its slot, scatter).
+        Stream order is all the synchronisation there is: the step launched next reads the blocks
+        behind the scatter, and a chunk reuses the staging buffer behind the copies out of it."""
+        spills, fills = self.sched.take_kv_moves()
+        if not spills and not fills:
+            return 0.0
+        t0 = time.perf_counter()
+        self._execute_kv_moves(spills, fills)
+        return time.perf_counter() - t0
+
+    def _execute_kv_moves(self, spills, fills):
+        """spills: [(block, slot)], fills: [(slot, block)] (benchmarks/host_kv_cache.py times it)."""
+        t0 = time.perf_counter()
+        pool, stage, cap = self._host_pool, self._host_stage, self._host_stage.shape[0]
+        nb = self.on_gpu
+        blocks = torch.tensor([b for b, _ in spills] + [b for _, b in fills], dtype=torch.int32)
+        if self.on_gpu:
+            blocks = blocks.pin_memory().to(self.device, non_blocking=True)
+        with torch.inference_mode():
+            for c0 in range(0, len(spills), cap):
+                ch = spills[c0:c0 + cap]
+                ops.kv_gather_blocks(self.kv.k, self.kv.v, blocks[c0:c0 + len(ch)], len(ch), stage)
+                for i, (_, slot) in enumerate(ch):
+                    pool[slot].copy_(stage[i], non_blocking=nb)
+            # a chunk never lists a block twice (a block filled, released and filled again within
+            # one schedule() call): the second fill runs in a later launch, so it lands last
+            c0, base = 0, len(spills)
+            while c0 < len(fills):
+                seen, m = set(), 0
+                while c0 + m < len(fills) and m < cap and fills[c0 + m][1] not in seen:
+                    seen.add(fills[c0 + m][1])
+                    m += 1
+                for i in range(m):
+                    stage[i].copy_(pool[fills[c0 + i][0]], non_blocking=nb)
+                ops.kv_scatter_blocks(self.kv.k, self.kv.v, blocks[base + c0:base + c0 + m], m, stage)
+                c0 += m
+        self.stats["host_move_s"] += time.perf_counter() - t0
+
+    def prefix_blocks(self, token_ids: Sequence[int]) -> List[Tuple[str, int]]:
+        """Where the leading full blocks of a prompt are cached: ("device", block id) or
+        ("host", slot) per 16-token block of its hash chain, up to the first miss. Takes no
+        reference and changes no LRU order. Call it between steps (not from another thread while
+        the engine loop runs)."""
+        return [("host" if tier else "device", int(i))
+                for tier, i in self.sched.prefix_blocks([int(t) for t in token_ids])]
 
     # ------------------------------------------------------------- pipelined steps
     def _step_pipelined(self) -> bool:
@@ -1821,6 +1948,11 @@ class LLMEngine:
             "kv_cache_gb": self.kv.k.numel() * 2 * 2 / 2**30,
             "weights_gb": self.model.weight_bytes() / 2**30,
             "weight_quant": self.model.weight_quant, "fp8_decode": self.model.fp8_decode,
+            "host_cache_blocks": self.host_cache_blocks, "num_host_cached": s.num_host_cached,  # blocks in the tier
+            "host_hit_blocks": s.host_hit_blocks, "host_spilled_blocks": s.host_spilled_blocks,
+            "host_evicted_blocks": s.host_evicted_blocks,
+            "host_cache_gb": 0.0 if self._host_pool is None else self._host_pool.numel() * 2 / 2**30,
+            "host_hit_tokens": s.host_hit_blocks * self.cfg.block_size,
         })
         if self.on_gpu:
             st["hbm_used_gb"] = torch.cuda.memory_allocated(self.device) / 2**30

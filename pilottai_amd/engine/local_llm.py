@@ -254,7 +254,9 @@ class LocalLLM(BaseLLM):
             from .registry import get_engine
 
             wq = _cfg_get(config, "weight_quant", None)
-            engine = get_engine(self.model_name, **({"weight_quant": wq} if wq is not None else {}))
+            hc = _cfg_get(config, "host_cache_gb", None)
+            engine = get_engine(self.model_name, **({"weight_quant": wq} if wq is not None else {}),
+                                **({"host_cache_gb": float(hc)} if hc is not None else {}))
         self.engine = engine
         # node-wide shared context (Serve.broadcast_context): a leading system
         # message whose KV every GPU pre-warmed into its prefix cache

@@ -30,6 +30,14 @@ def get_engine(model: str = "llama-3-8b", **overrides) -> LLMEngine:
             if have != overrides["weight_quant"]:
                 raise ValueError(f"this process already holds an engine for {key!r} with weight_quant={have!r} "
                                  f"(asked for {overrides['weight_quant']!r}): one engine per model per process")
+        if eng is not None and "host_cache_gb" in overrides:
+            # the effective size: an engine sized by host_cache_blocks has no host_cache_gb to compare
+            have = int(getattr(eng, "host_cache_blocks", 0))
+            want = int(float(overrides["host_cache_gb"]) * (1 << 30)) // max(1, int(getattr(eng, "kv_block_bytes", 1)))
+            if have != want:
+                raise ValueError(f"this process already holds an engine for {key!r} with a host KV tier of {have} "
+                                 f"blocks (host_cache_gb={overrides['host_cache_gb']!r} asks for {want}): "
+                                 "one engine per model per process")
         if eng is None:
             kw = dict(_DEFAULTS.get(key, {}))
             kw.update(overrides)

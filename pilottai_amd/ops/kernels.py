@@ -136,6 +136,26 @@ def kv_copy(k_cache, v_cache, n_copies, copies) -> None:
     ref.kv_copy(k_cache, v_cache, n_copies, copies)
 
 
+def kv_gather_blocks(k_cache, v_cache, ids, n: int, stage) -> None:
+    """Host tier of the prefix cache (csrc/ops/kv_pages.hip): for i < n, every layer's K and V
+    pages of block `ids[i]` go to record i of `stage` [records, layers * 2 * KV * 2048], laid
+    out [layer][K|V][KV][page]. `ids` is an int32 tensor on the caches' device, `n` a plain
+    number (not graph-capturable); an id outside [0, blocks) leaves its record alone."""
+    if _on_gpu(k_cache):
+        require_native().kv_gather_blocks(k_cache, v_cache, ids, int(n), stage)
+        return
+    ref.kv_gather_blocks(k_cache, v_cache, ids, n, stage)
+
+
+def kv_scatter_blocks(k_cache, v_cache, ids, n: int, stage) -> None:
+    """The inverse of kv_gather_blocks: record i of `stage` goes to the pages of block `ids[i]`;
+    nothing outside the listed blocks is written."""
+    if _on_gpu(k_cache):
+        require_native().kv_scatter_blocks(k_cache, v_cache, ids, int(n), stage)
+        return
+    ref.kv_scatter_blocks(k_cache, v_cache, ids, n, stage)
+
+
 def span_pool(hn, n_seg, segs, pool) -> None:
     """Span pooling (csrc/ops/span_pool.hip): for each of the first `n_seg[0]` (first_row, n_rows,
     slot, init) quadruples of `segs`, pool[slot] = (0 if init else pool[slot]) + hn[first_row] + ...

@@ -113,6 +113,32 @@ def kv_copy(k_cache, v_cache, n_copies, copies):
         v_cache[:, dst, :, :, :j] = v_cache[:, src, :, :, :j]
 
 
+def _kv_records(k_cache, stage):
+    layers, blocks, KV = k_cache.shape[:3]
+    return stage.view(stage.shape[0], layers, 2, KV, -1), blocks
+
+
+def kv_gather_blocks(k_cache, v_cache, ids, n, stage):
+    """stage [records, layers * 2 * KV * 2048]: record i = [layer][K|V][KV][page] of block ids[i]
+    for i < n; ids outside [0, blocks) are skipped."""
+    rec, blocks = _kv_records(k_cache, stage)
+    for i, b in enumerate(ids.reshape(-1)[: int(n)].tolist()):
+        if not 0 <= b < blocks:
+            continue
+        rec[i, :, 0] = k_cache[:, b].reshape(rec.shape[1], rec.shape[3], -1)
+        rec[i, :, 1] = v_cache[:, b].reshape(rec.shape[1], rec.shape[3], -1)
+
+
+def kv_scatter_blocks(k_cache, v_cache, ids, n, stage):
+    """The inverse of kv_gather_blocks: record i goes to block ids[i]."""
+    rec, blocks = _kv_records(k_cache, stage)
+    for i, b in enumerate(ids.reshape(-1)[: int(n)].tolist()):
+        if not 0 <= b < blocks:
+            continue
+        k_cache[:, b] = rec[i, :, 0].reshape(k_cache[:, b].shape)
+        v_cache[:, b] = rec[i, :, 1].reshape(v_cache[:, b].shape)
+
+
 def span_pool(hn, n_seg, segs, pool):
     """hn [T, d] bf16, pool [slots, d] fp32 (updated in place): for each of the first n_seg[0]
     (first_row, n_rows, slot, init) quadruples, the rows are added to the slot's accumulator one by

@@ -334,7 +334,11 @@ def create_app(llm, model_name: Optional[str] = None, engine=None) -> FastAPI:
         if eng is not None:
             if getattr(eng, "failed", None) is not None:
                 return JSONResponse({"status": "failed", "error": str(eng.failed)}, status_code=503)
-            out["engine"] = eng.metrics()
+            out["engine"] = m = eng.metrics()
+            # the host KV tier (EngineConfig.host_cache_gb; all 0 while it is off)
+            for k in ("host_cache_gb", "host_hit_tokens", "host_spilled_blocks"):
+                out[k] = m.get(k, 0)
+            out["host_cached_blocks"] = m.get("num_host_cached", 0)
         return out
 
     @app.get("/v1/models")
@@ -523,6 +527,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="quantise the layer projections (fp8: e4m3, per-channel power-of-two scales)")
     ap.add_argument("--no-fp8-decode", dest="fp8_decode", action="store_false",
                     help="with --weight-quant fp8: keep decode steps on the bf16 kernels (no FP8 copy in HBM)")
+    ap.add_argument("--host-cache-gb", type=float, default=0.0,
+                    help="pinned host memory for KV blocks evicted from the prefix cache (GiB; 0 = off): "
+                         "a prompt whose prefix was spilled there gets it copied back instead of recomputed")
     return ap
 
 
@@ -546,7 +553,7 @@ def main():
                                      kv_cache_gb=a.kv_gb if dev.type == "cuda" else None,
                                      num_kv_blocks=None if dev.type == "cuda" else 1024,
                                      freeze_heap=True, weight_quant=a.weight_quant,
-                                     fp8_decode=a.fp8_decode), device=dev)
+                                     fp8_decode=a.fp8_decode, host_cache_gb=a.host_cache_gb), device=dev)
         eng.start()
         llm = LocalLLM(LLMConfig(model_name=eng.model_cfg.name, max_tokens=1024), engine=eng)
         app = create_app(llm, eng.model_cfg.name, engine=eng)
